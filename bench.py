@@ -6,8 +6,11 @@ reset to an empty HDDStream, the exact per-point online phase over N points (cc_
 PreDeCon phase (cc_offline) with the export of all clusters.
 
 At N GPUs the headline `value` is N independent event streams of the C2 shape, one per rank (weak scaling, no
-data-path collective: the online phase of one stream is a sequential chain over its points).  The same JSON line
-also carries, as side legs (strong scaling: ONE stream, all N GPUs):
+data-path collective: the online phase of one stream is a sequential chain over its points).  A plain run measures the
+headline alone (with the scan's `roofline`, from the timed steps' own kernel timing).  With --full the same JSON line
+also carries the side measurements: the step with its transfers inside the timed region (`value_with_transfers`), the
+step outside the friendliest regime (`general_regimes`), the CPU baseline (`cpu_baseline`) and, as side legs (strong
+scaling: ONE stream, all N GPUs):
   one_stream_exact            the stress config's shape (d = 40, 50 000 microclusters), exact: snapshot scans split by
                               table rows, one RCCL all-gather of 64 B per window point, offline pair matrices split by
                               rows, with a check that every rank ended with the same bytes
@@ -23,7 +26,9 @@ Every leg carries `n_gpus`, `collective`, `rccl_ranks_seen` and a `roofline` obj
 No torch anywhere: the timing bracket is cc_sync (HIP stream synchronise through the C-ABI), barrier / max over
 ranks / the 128-byte RCCL id travel over chronoclust_amd.rendezvous (TCP on 127.0.0.1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+        --dump-outputs DIR: after the timed steps, what the last step computed (rank 0's stream) as DIR/<name>.npy in
+        float64 (dump_outputs below); the inputs are seeded, so two builds run with the same arguments compare file by file
         N > 1 and no launcher's RANK / WORLD_SIZE in the environment: THIS process starts the N ranks itself - fresh
         child processes, one per GPU (LOCAL_RANK = device), before anything here has touched HIP or RCCL -, relays
         rank 0's line and exits with the worst child's status (launch_ranks below)
@@ -131,6 +136,36 @@ def newest_pmc(pattern):
 DETAIL_FILE = os.environ.get("CHRONOCLUST_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json"))
 LINE_LIMIT = 4096   # bytes of the ONE stdout line (tests/test_host_logic.py::test_bench_line_is_compact holds it)
 LEG_NAMES = ("one_stream_exact", "events_sharded_relaxed", "one_stream_exact_c2", "events_sharded_relaxed_c2")
+DUMP_LIMIT = 64_000_000  # bytes of all the .npy files --dump-outputs writes
+DUMP_SEED = 20240611     # of the row sample an output larger than DUMP_LIMIT is cut to
+
+
+def step_outputs(uid, path, arrays):
+    """What a caller of the timed step receives, by name: the per-point labels of the online phase (microcluster
+    creation number, path taken) and the clusters of the offline phase (Handle.offline_arrays)."""
+    mem, off, w, cf1, cf2, cen, pref = arrays
+    return {"point_uid": uid, "point_path": path, "cluster_members": mem, "cluster_offsets": off, "cluster_w": w,
+            "cluster_cf1": cf1, "cluster_cf2": cf2, "cluster_cen": cen, "cluster_pref": pref}
+
+
+def dump_outputs(directory, named, limit=DUMP_LIMIT):
+    """Writes every array of `named` as <directory>/<name>.npy in float64 (ids and counts stay exact below 2^53).  When
+    they would take more than `limit` bytes together, every array is cut to the same fraction of its rows - a sample
+    seeded by DUMP_SEED and the row count alone, so the same on every run - and the row numbers go to <name>_rows.npy.
+    Returns the names written."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in named.items()}
+    budget = limit - 256 * 2 * len(arrays)  # (an .npy header is 128 bytes; the row files have one each as well)
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        frac = budget / sum(a.nbytes + 8 * a.shape[0] for a in arrays.values())
+        for name, a in list(arrays.items()):
+            rows = np.sort(np.random.default_rng((DUMP_SEED, a.shape[0])).choice(a.shape[0], int(a.shape[0] * frac),
+                                                                                  replace=False))
+            arrays[name] = a[rows]
+            arrays[name + "_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def _r(x, digits=6):
@@ -896,6 +931,11 @@ def main():
     ap.add_argument("--lookahead", type=int, default=0, help="0/1 on (default), 2 off, 3 forced")
     ap.add_argument("--early-window", type=int, default=0, help="window while the table grows / is being promoted (0: 4096)")
     ap.add_argument("--windows-per-sync", type=int, default=0, help="windows enqueued between host read-backs (0: 16)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, the side measurements as well: transfers inside the timed region, general "
+                         "regimes, CPU baseline, strong-scaling legs (the --no-* options below leave parts of them out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, float64, at most 64 MB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-general-regimes", action="store_true", help="skip the step with the pdim filter on / k not a power of two")
     ap.add_argument("--no-transfers", action="store_true", help="skip the transfer-inclusive measurement (upload + labels inside the timed region)")
@@ -919,12 +959,13 @@ def main():
     ap.add_argument("--relaxed-minibatch", type=int, default=262144,
                     help="points per rank and super-step (eight windows: lookahead scans inside a super-step; 65 536 - two windows per call - measured half the rate on one rank)")
     ap.add_argument("--no-c2-legs", action="store_true", help="skip the two C2-shaped strong-scaling legs")
-    ap.add_argument("--only-leg", default=None, help="profiling: only this leg, after a token headline (20 000 points, 100 microclusters, no CPU baseline)")
+    ap.add_argument("--only-leg", default=None, help="profiling: only this leg, after a token headline (20 000 points, 100 microclusters, no CPU baseline); implies --full")
     ap.add_argument("--dry-launch", action="store_true", help="the ranks only rendezvous and rank 0 prints who came (no GPU is touched)")
     ap.add_argument("--shard-min-row-dims", type=int, default=None,
                     help="one-stream legs: a snapshot scan is split over the ranks from this many (row, dim) entries on "
                          "(default: what the library measured when the group was formed, cc_comm_calibrate)")
     args = ap.parse_args()
+    full = args.full or args.only_leg is not None
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # no launcher: start the N ranks from here (nothing in this process has loaded the HIP library)
         sys.stdout.flush()
@@ -972,12 +1013,14 @@ def main():
                  time_kernels=0 if args.no_kernel_timing else 1)
     set_params(h, cfg, n, d)
     h.points_upload(X)  # inputs are resident in HBM before the timed region
+    last = {}
 
     def step():
         h.reset()
         h.online_run()
         s = h.stats()
         arrays, _ = h.offline_arrays()  # cc_offline + cc_clusters_export: every cluster's members and CF vectors on the host
+        last["arrays"] = arrays
         return s, len(arrays[2])
 
     def sync(handle):
@@ -1004,7 +1047,9 @@ def main():
     sync(h)
     elapsed = time.perf_counter() - t0
     elapsed = multi.max_over_ranks(elapsed, group)
-    uid, _ = h.labels_download()
+    uid, path = h.labels_download()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(uid, path, last["arrays"]))
 
     out = None
     if rank == 0:
@@ -1058,25 +1103,25 @@ def main():
             elif (pmc.get("points"), pmc.get("dim"), pmc.get("window")) == (n, d, out["config"]["window"]):
                 out["roofline"]["traffic"] = pmc["k_scan_clean_bytes_per_launch"]
                 out["roofline"]["traffic_note"] = "profiles/%s: %s" % (name, pmc["note"])
-        if world == 1 and not args.no_transfers and not args.only_leg:
+        if full and world == 1 and not args.no_transfers and not args.only_leg:
             wt = with_transfers(h, X, max(2, min(args.steps, 10)), step)
             out["with_transfers"] = wt
             out["value_with_transfers"] = wt["value"]
-        if world == 1 and not args.no_cpu_baseline and not args.only_leg:
+        if full and world == 1 and not args.no_cpu_baseline and not args.only_leg:
             # (the GPU box gives a one-GPU job 16 of the host's cores; os.cpu_count() reports the whole machine)
             usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             from chronoclust_amd import _lib as _L
             out["cpu_baseline"] = cpu_baseline(cfg, X, args.cpu_sample, max(1, min(usable, args.cpu_cores)), uid,
                                                gpu_tables=(h.export(_L.PCORE), h.export(_L.OUTLIER)))
             out["cpu_baseline"]["host_cpu_count"] = os.cpu_count()
-        if world == 1 and not args.no_transfers and not args.no_general_regimes and not args.only_leg:
+        if full and world == 1 and not args.no_transfers and not args.no_general_regimes and not args.only_leg:
             # the same step outside the friendliest regime (pi = d, k = 4): the pdim filter of hddstream.py:317-321 on, k not a
             # power of two - pruned scans there since round 6 (k_scan_p3<GENERAL> behind seeded thresholds)
             out["general_regimes"] = general_regimes(h, cfg, n, d, step, max(2, min(args.steps, 6)))
             out["filter_on_points_per_s"] = out["general_regimes"]["filter_pi_d_minus_2"]["value"]
     h.close()
     del X
-    if rank == 0:
+    if rank == 0 and full:
         out["strong_scaling"] = {
             "note": "`value` above is N independent streams (one per GPU, no data-path collective); the entries here are ONE "
                     "stream clustered by all %d rank(s): points of that one stream per second.  The 20-dim metric's own "
@@ -1085,12 +1130,12 @@ def main():
             "n_gpus": world, "rccl_ranks_seen": None}
         guard.provisional(out)  # from here on the headline is safe whatever happens to the legs below
 
-    legs = []
-    if not args.no_one_stream:
+    legs = []  # (a plain run: the headline alone)
+    if full and not args.no_one_stream:
         legs.append(("one_stream_exact", one_stream_exact))
-    if not args.no_relaxed:
+    if full and not args.no_relaxed:
         legs.append(("events_sharded_relaxed", events_sharded_relaxed))
-    if not args.no_c2_legs:
+    if full and not args.no_c2_legs:
         legs.append(("one_stream_exact_c2", one_stream_exact_c2))
         legs.append(("events_sharded_relaxed_c2", events_sharded_relaxed_c2))
     if args.only_leg:

@@ -10,6 +10,7 @@ import subprocess
 import sys
 import textwrap
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -132,3 +133,35 @@ def test_keeper_prints_exactly_one_line(tmp_path, mode, nonblocking):
     with open(detail) as f:
         full = json.load(f)
     assert "executed" in full["roofline"] and "one_stream_exact" in full  # (the detail keeps everything)
+
+
+def _step_outputs(n, clusters, d):
+    rng = np.random.default_rng(5)
+    off = np.arange(clusters + 1, dtype=np.int32) * 3
+    arrays = (rng.integers(0, 1 << 40, 3 * clusters), off, rng.random(clusters), *(rng.random((clusters, d)) for _ in range(4)))
+    return bench.step_outputs(rng.integers(0, 1 << 40, n), rng.integers(0, 3, n).astype(np.int8), arrays)
+
+
+def test_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """--dump-outputs: every array a caller of the timed step receives, as <name>.npy in float64, values unchanged."""
+    named = _step_outputs(1000, 7, 20)
+    names = bench.dump_outputs(str(tmp_path), named)
+    assert names == sorted(named) and sorted(p.name for p in tmp_path.iterdir()) == sorted(k + ".npy" for k in named)
+    for k, v in named.items():
+        a = np.load(str(tmp_path / (k + ".npy")))
+        assert a.dtype == np.float64 and a.shape == v.shape and np.array_equal(a, v), k
+
+
+def test_dump_outputs_samples_the_same_rows_below_the_limit(tmp_path):
+    """Larger than the limit: a seeded sample of rows, the same on every run, all files together within the limit."""
+    named = _step_outputs(200_000, 50, 20)
+    limit = 1_000_000
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), named, limit=limit)
+        assert sum(p.stat().st_size for p in (tmp_path / run).iterdir()) <= limit
+    rows = np.load(str(tmp_path / "a" / "point_uid_rows.npy")).astype(np.int64)
+    assert 0 < len(rows) < 200_000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "point_uid.npy")), named["point_uid"][rows])
+    assert np.array_equal(np.load(str(tmp_path / "a" / "point_path_rows.npy")), rows)  # (same length, same rows)
+    for p in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(str(p)), np.load(str(tmp_path / "b" / p.name))), p.name

@@ -9,7 +9,7 @@ mkdir -p $OUT
 L="python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1"
 timeout -k 10 240 $L --master-port 29611 bench.py --gpus 2 --share-gpu --steps 2 --warmup 1 --no-one-stream --no-relaxed --no-c2-legs > $OUT/n2_headline.json 2> $OUT/n2_headline.err
 echo "headline: exit $?" | tee $OUT/n2_status.txt
-timeout -k 10 300 $L --master-port 29612 bench.py --gpus 2 --share-gpu --steps 1 --warmup 0 --no-relaxed --no-c2-legs --stream-points 200000 --stream-blobs 5000 --stream-timeout 30 --strict-legs > $OUT/n2_leg.json 2> $OUT/n2_leg.err
+timeout -k 10 300 $L --master-port 29612 bench.py --gpus 2 --share-gpu --steps 1 --warmup 0 --full --no-relaxed --no-c2-legs --stream-points 200000 --stream-blobs 5000 --stream-timeout 30 --strict-legs > $OUT/n2_leg.json 2> $OUT/n2_leg.err
 echo "leg on a shared GPU: launcher exit $? (1 expected: the launcher's code for failed ranks; the ranks themselves exit 3, see below)" | tee -a $OUT/n2_status.txt
 python - $OUT <<'PY' | tee -a $OUT/n2_status.txt
 import json, sys

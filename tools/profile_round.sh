@@ -13,7 +13,7 @@ cd "${GRAFT_REPO_ROOT:?run on the GPU box (gpurun exports GRAFT_REPO_ROOT)}" || 
 B="python bench.py --no-cpu-baseline --no-transfers --no-one-stream --no-relaxed --no-c2-legs"
 if want bench; then
 # the driver's literal command; the line on stdout, the full record in the detail file beside it
-CHRONOCLUST_BENCH_DETAIL=$OUT/bench_detail.json python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+CHRONOCLUST_BENCH_DETAIL=$OUT/bench_detail.json python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
 python - $OUT/bench.json <<'PY' || exit 1
 import json, sys
 text = open(sys.argv[1]).read()
@@ -38,7 +38,7 @@ fi
 if want legs; then
 # the two legs whose scans run at d = 40 / d = 14 (one_stream_exact: C5-shaped, events_sharded_relaxed: C4-shaped)
 for LEG in one_stream_exact events_sharded_relaxed; do
-  CHRONOCLUST_BENCH_DETAIL=$OUT/bench_leg_${LEG}_detail.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$LEG -o r -- python bench.py --only-leg $LEG --steps 1 --warmup 0 > $OUT/bench_leg_$LEG.json 2> $OUT/trace_$LEG.err || exit 1
+  CHRONOCLUST_BENCH_DETAIL=$OUT/bench_leg_${LEG}_detail.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$LEG -o r -- python bench.py --full --only-leg $LEG --steps 1 --warmup 0 > $OUT/bench_leg_$LEG.json 2> $OUT/trace_$LEG.err || exit 1
   python tools/prof_summary.py $OUT/trace_$LEG > $OUT/kernel_summary_leg_$LEG.txt
   python tools/scan_chain_summary.py $OUT/trace_$LEG $OUT/bench_leg_${LEG}_detail.json $LEG > $OUT/scan_chain_leg_$LEG.json
 done

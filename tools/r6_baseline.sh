@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/r6base}
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:?run on the GPU box}" || exit 1
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 cp bench_detail.json $OUT/bench_detail.json
 REPS=3 python3 tools/startup.py > $OUT/startup.txt 2>&1 || exit 1
 REPS=2 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o r -- python3 tools/startup.py > $OUT/trace.txt 2>&1 || exit 1
