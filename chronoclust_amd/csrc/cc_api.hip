@@ -143,6 +143,26 @@ struct PinArena {
     ~PinArena() { if (p) (void)hipHostFree(p); }
 };
 
+// How the clean snapshot scans of an online call run for the handle's d, pdim filter, k and knobs (scan_plan(): read by the
+// dispatcher, the window policy's configuration and the partial counts).  Two thresholds are in table rows, which grow.
+struct ScanPlan {
+    int dp = 0;            // padded dimensionality: the ladder 4 / 8 / 14 / 16 / 20 / 32 / 40 / 64 (0: not planned yet)
+    bool scan_u = false;   // the plain scan is k_scan_u (k a power of two, no pdim filter, d on the ladder), else k_scan<FILTER, POW2>
+    // the pruned chain: COMMON where k_scan_u applies and d > 8; GENERAL (k_scan_p3<GENERAL>) where the pdim filter is on or k
+    // is not a power of two
+    enum Chain { NONE, COMMON, GENERAL } chain = NONE;
+    // its scan of a window: k_scan_p3, k_scan_p2 or k_scan_p - the split form k_scan_a + k_scan_p<MASKED> from split_rows table
+    // rows on -; k_scan_p3 LISTED from listed_rows table rows on
+    enum Form { P3, P2, P1 } form = P1;
+    long long split_rows = std::numeric_limits<long long>::max(), listed_rows = 0;
+    bool seed16 = false;  // the window's seeded chain: seeds from k_seed16 with the tight threshold, not from k_seed
+    int prune_applicable = 0, allow_guess = 0, allow_probe = 0, force_prune_rows = 0;  // (cc_policy_config)
+    int waves = 4, dirty_waves = 4;  // waves per workgroup of the clean / dirty scans
+    int plain_wgs_per_cu = 1, prune_wgs_per_cu = 1;  // resident workgroups of the plain scan / those a pruned one is split into
+    bool split(long long m_rows) const { return m_rows >= split_rows; }
+    bool listed(long long m_rows) const { return m_rows >= listed_rows; }
+};
+
 struct cc_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -177,6 +197,7 @@ struct cc_handle {
     bool lean_now = false;    // ... guessed thresholds without k_missed / the seeded chain for missed points (cc_policy_decision::prune == 3)
     bool guess_now = false;   // ... with guessed thresholds (k_scan_p + k_missed + the seeded chain for the missed points)
     bool probe_now = false;   // the next plain scan also runs the pruned chain on 128 points (cc_policy_decision::probe)
+    ScanPlan scan_plan;       // how this call's snapshot scans run (set per online call by OnlineRun::prepare)
     DevBuf<Cand> probe_part;  // ... into these scratch partials
     bool allow_guess = true;  // CHRONOCLUST_HIP_GUESS=0: seeded thresholds only
     bool allow_lean = true;   // CHRONOCLUST_HIP_LEAN=0: guessed scans always list and rescan the points they missed
@@ -609,9 +630,6 @@ Versions versions_view(cc_handle* h)
 
 // ---- scan dispatch over the padded dimensionality ---------------------------------
 
-// does the snapshot scan of this handle's stream run as k_scan_u? (decided per launch by the same test)
-bool scan_u_applies(const cc_handle* h, int DP) { return h->allow_scan_u && h->hc.filter == 0 && h->hc.pow2 && h->d == DP; }
-
 // the table rows as half-precision operands of the MFMA prefix test (k_prefix16): two window parities, whole tiles of 32 rows
 // (grown between batches only: a scan in flight on the other stream may be reading it)
 void ensure_prefix16(cc_handle* h)
@@ -625,12 +643,162 @@ void ensure_prefix16(cc_handle* h)
     h->hdr16.ensure(2);
 }
 
-// does a PRUNED snapshot scan of this handle run as k_scan_p3<GENERAL> - the pdim filter on and / or k not a power of two?
-// (the plain scans of these cases stay with k_scan<FILTER, POW2>)
-bool scan_p3_general_applies(const cc_handle* h, int DP)
+// From here to launch_scan: the scan plan, the launch helpers and the dispatcher - the host code that sets the snapshot
+// scan's launch geometry (bench.py's scan_digest() hashes this text)
+template <int DP, bool DIRTY>
+void launch_scan_dp(cc_handle* h, hipStream_t st, int win, Rows rows, const Cand* clean, Cand* part, int S, int round,
+                    int mode, int shard_rank, int shard_world, int phase);
+
+// workgroups per CU of k_scan_u that are resident at once (what it is compiled for if the runtime does not say)
+template <int DP>
+int scan_u_wgs_per_cu()
 {
-    return h->allow_scan_p3 && h->allow_prune_general && h->d == DP && DP > 8 && DP <= 40 && (h->hc.filter != 0 || !h->hc.pow2);
+    constexpr int NW = ScanShape<DP, false>::NW;
+    static int blocks = 0;
+    static const bool ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_scan_u<DP, NW>, 64 * NW, 0) == hipSuccess && blocks >= 1;
+    return ok ? blocks : ScanUShape<DP>::WGS;
 }
+
+template <int DP>
+ScanPlan scan_plan_dp(const cc_handle* h)
+{
+    ScanPlan p;
+    p.dp = DP;
+    const bool filter = h->hc.filter != 0, pow2 = h->hc.pow2 != 0;
+    // the common case (k a power of two, no pdim filter, no padded dimensions): rows as scalar operands
+    p.scan_u = h->allow_scan_u && !filter && pow2 && h->d == DP;
+    if (p.scan_u && DP > 8) p.chain = ScanPlan::COMMON;
+    else if (h->allow_scan_p3 && h->allow_prune_general && h->d == DP && DP > 8 && DP <= 40 && (filter || !pow2))
+        p.chain = ScanPlan::GENERAL;
+    // the window's pruned scan: phase A on the matrix cores (k_scan_p3; GENERAL needs it), two points per lane (k_scan_p2) or
+    // one (k_scan_p); CHRONOCLUST_HIP_SCANA: 0 never the split form, 2 always (even over k_scan_p3), 1 from 10 000 table rows
+    // on where k_scan_p3 does not run.  The GENERAL chain is never split.
+    const bool p3 = h->allow_scan_p3 && DP <= 40;
+    p.form = p3 ? ScanPlan::P3 : (h->allow_scan_p2 && DP <= 40 ? ScanPlan::P2 : ScanPlan::P1);
+    if (p.chain == ScanPlan::COMMON && h->split_a_mode == 2) p.split_rows = 0;
+    else if (p.chain == ScanPlan::COMMON && h->split_a_mode == 1 && !p3) p.split_rows = 10000;
+    p.listed_rows = h->p3_listed_rows;
+    // (k_scan_p3 as SCANA sees it, on the GENERAL chain too: where the seeds come from the matrix cores, the pruned partials)
+    const bool p3_sized = p3 && h->split_a_mode != 2;
+    p.seed16 = h->allow_seed16 && (p.chain == ScanPlan::GENERAL || p3_sized);
+    p.prune_applicable = p.chain != ScanPlan::NONE ? 1 : 0;
+    // (GENERAL: seeded thresholds only - the points a guessed threshold misses would need a plain scan over a point list, which
+    // exists for the common case alone (k_scan_u) -, no probes)
+    p.allow_guess = (h->allow_guess && p.chain != ScanPlan::GENERAL) ? (h->allow_lean ? 1 : 2) : 0;  // (2: guessed thresholds, never lean)
+    p.allow_probe = (h->allow_probe && p.chain != ScanPlan::GENERAL) ? 1 : 0;
+    // (pruned scans from this many rows on whatever the phase: where the seeded chain runs behind k_seed16)
+    p.force_prune_rows = (p.prune_applicable && h->allow_seed16 && p3_sized) ? h->force_prune_rows : 0;
+    p.waves = ScanShape<DP, false>::NW;
+    p.dirty_waves = ScanShape<DP, true>::NW;
+    p.plain_wgs_per_cu = p.scan_u ? scan_u_wgs_per_cu<DP>() : ScanShape<DP, false>::WGS;
+    // (measured, `profiles/r03_tool_prune_split.txt`: four rounds of the resident workgroups at d <= 20 - k_scan_p is
+    // compiled for four per CU there -, eight of the three per CU beyond)
+    // (round 6, k_scan_p3: the prefix test costs next to nothing on the matrix cores, what is left of a workgroup's time is its
+    // prologue - the points staged, their constants - and the rows it completes: two rounds of the resident workgroups at
+    // d <= 20, 54 against 63 us per C2 window running alone, half the partials per point)
+    p.prune_wgs_per_cu = h->prune_rounds4 > 0 ? h->prune_rounds4 : (DP <= 20 ? (p3_sized ? 8 : 16) : 24);
+    return p;
+}
+
+ScanPlan scan_plan(const cc_handle* h)
+{
+    // (padded dimensions cost full distance terms: the ladder follows the shapes of BASELINE.json - d = 14, 20, 40)
+    const int d = h->d;
+    return d <= 4 ? scan_plan_dp<4>(h) : d <= 8 ? scan_plan_dp<8>(h) : d <= 14 ? scan_plan_dp<14>(h) : d <= 16 ? scan_plan_dp<16>(h)
+         : d <= 20 ? scan_plan_dp<20>(h) : d <= 32 ? scan_plan_dp<32>(h) : d <= 40 ? scan_plan_dp<40>(h) : scan_plan_dp<64>(h);
+}
+
+// The clean scan's launches at padded width DP, one helper per kernel family: the window's `win` points, S partials per
+// point into `part` (at the handle's part_stride), or lists of points
+template <int DP>
+struct ScanCall {
+    static constexpr int NW = ScanShape<DP, false>::NW;
+    cc_handle* h; hipStream_t st; const Rows& rows;
+    int round, mode, win, S;
+    Cand* part;
+
+    // k_scan_u over the window (n_pts = win, plist == nullptr) or a list
+    void scan_u(int n_pts, int srank, int sworld, const int* plist) const
+    {
+        hipLaunchKernelGGL((k_scan_u<DP, NW>), dim3((n_pts + 63) / 64, S), dim3(64 * NW), 0, st, h->ctl.p, h->Xt.p, rows.cen,
+                           rows.scl, rows.kind, rows.key, part, round, mode, h->part_stride, srank, sworld, plist);
+    }
+    // the rows as half-precision operands of the MFMA prefix test (k_scan_p3, k_seed16)
+    void prefix16() const
+    {
+        ensure_prefix16(h);
+        const size_t a16_rows = h->tab.cap + 2 * CC_P16_TM;
+        hipLaunchKernelGGL((k_prefix16<DP>), dim3((unsigned)((a16_rows + 255) / 256)), dim3(256), 0, st, (const Ctl*)h->ctl.p,
+                           rows.cen, rows.kind, h->a16.p, h->hdr16.p, h->a16_stride, round, mode);
+    }
+    // seeds for n_pts points of the window or a list, Sp partials per point - k_seed (two points per lane: point tiles of 128)
+    // or from the matrix cores (k_seed16, behind prefix16()) -, then the thresholds (k_seed_merge: F x the nearest seed; the
+    // tight one, F <= 0, behind k_seed16)
+    void seeds(int n_pts, int Sp, const int* plist, bool s16) const
+    {
+        const dim3 grid((n_pts + 127) / 128, Sp), block(64 * NW);
+        if (s16) {
+            if constexpr (DP <= 40) {
+                hipLaunchKernelGGL((k_seed16<DP, NW>), grid, block, 0, st, (const Ctl*)h->ctl.p, (const double*)h->Xt.p, rows.cen, h->spart.p,
+                                   round, mode, h->spart_stride, (const cc_h8*)h->a16.p, (const Prefix16Hdr*)h->hdr16.p, h->a16_stride);
+                ++h->stats.seed16_launches;
+            } else {
+                throw HipErr{hipErrorInvalidValue, "k_seed16 is compiled up to 40 dimensions"};
+            }
+        } else {
+            hipLaunchKernelGGL((k_seed<DP, NW>), grid, block, 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.kind, h->spart.p, round, mode,
+                               h->spart_stride, h->cmax.p, plist);
+        }
+        hipLaunchKernelGGL((k_seed_merge<DP>), dim3((2 * n_pts + 63) / 64), dim3(64), 0, st, h->ctl.p, h->X.p, rows.cen, rows.scl, h->spart.p,
+                           h->spart_stride, Sp, h->thr.p, h->thr32.p, h->thr_stride, s16 ? 0.0 : h->prune_F, round, mode, h->cmax.p,
+                           h->pstat_p(), plist);
+    }
+    // k_scan_p3 over the window (behind prefix16()); GENERAL evaluates the pdim filter (lazily, for rows that would enter a
+    // list) and divides by k itself
+    template <bool LISTED, bool GENERAL>
+    void scan_p3(unsigned lds, int srank, int sworld, double gF, unsigned long long* found) const
+    {
+        hipLaunchKernelGGL((k_scan_p3<DP, NW, LISTED, GENERAL>), dim3((win + 127) / 128, S), dim3(64 * NW), lds, st, h->ctl.p, h->Xt.p,
+                           rows.cen, rows.scl, rows.kind, rows.key, h->thr.p, h->thr_stride, part, round, mode, h->part_stride, srank,
+                           sworld, h->pstat_p(), gF, found, (const cc_h8*)h->a16.p, (const Prefix16Hdr*)h->hdr16.p, h->a16_stride,
+                           GENERAL ? (const double*)h->X.p : nullptr, GENERAL ? rows.cf1 : nullptr, GENERAL ? rows.cf2 : nullptr,
+                           GENERAL ? rows.w : nullptr);
+    }
+    // k_scan_p, one point per lane with phase A inside: n_pts points of the window or a list, Sp partials per point into p
+    void scan_p(int n_pts, int Sp, Cand* p, size_t p_stride, int srank, int sworld, const int* plist, double gF,
+                unsigned long long* found) const
+    {
+        hipLaunchKernelGGL((k_scan_p<DP, NW, false>), dim3((n_pts + 63) / 64, Sp), dim3(64 * NW), 0, st, h->ctl.p, h->Xt.p, rows.cen,
+                           rows.scl, rows.kind, rows.key, h->thr.p, h->thr32.p, h->thr_stride, p, round, mode, p_stride, srank, sworld,
+                           h->pstat_p(), plist, gF, found, (const unsigned*)nullptr, (size_t)0, 0, 1);
+    }
+    // the window's pruned scan as two kernels: phase A (k_scan_a: two points per lane, survivor masks), phase B behind it
+    void scan_split(int srank, int sworld, double gF, unsigned long long* found) const
+    {
+        const int nsub = S * NW;
+        const int tps = cc_mask_tiles_per_sub((int)std::min<size_t>(h->tab.cap, (size_t)INT_MAX - 64), nsub);
+        const size_t need = (size_t)((win + 127) / 128) * (size_t)nsub * (size_t)tps;
+        if (need > h->mask_stride) { h->masks.ensure(2 * need); h->mask_stride = need; }
+        hipLaunchKernelGGL((k_scan_a<DP, NW>), dim3((win + 127) / 128, S), dim3(64 * NW), 0, st, (const Ctl*)h->ctl.p,
+                           (const double*)h->Xt.p, rows.cen, rows.kind, (const double*)h->thr.p, h->thr_stride, h->masks.p,
+                           h->mask_stride, tps, round, mode, srank, sworld, gF);
+        // phase B: about one and a half rounds of the resident workgroups, i.e. q of phase A's sub-ranges per wave
+        // (its waves live on chains of memory round trips - prologue, masks, a few rows, merge -, not on arithmetic:
+        // with phase A's own split - eight rounds at the C5 shape - the prologues dominate, with one round every
+        // wave walks q times the rows; 2 M x 40, 50 000 rows: q = 1 / 2 / 3 / 4 / 6 / 12 -> 39.6 / 40.6 / 40.7 /
+        // 41.2 / 39.9 / 39.8 M points/s.  CHRONOCLUST_HIP_SCANB_Q overrides.)
+        int q = 1;
+        const int tiles = (win + 63) / 64;
+        const int resident = h->n_cus * (DP <= 20 ? CC_SCANP_WGS20 : (DP <= 40 ? 3 : 2));
+        for (int c = 1; c <= S; ++c)
+            if (S % c == 0 && 2 * tiles * (S / c) >= 3 * resident) q = c;
+        static const int q_env = []() { const char* e = getenv("CHRONOCLUST_HIP_SCANB_Q"); return e ? atoi(e) : 0; }();
+        if (q_env > 0 && S % q_env == 0) q = q_env;
+        hipLaunchKernelGGL((k_scan_p<DP, NW, true>), dim3(tiles, S / q), dim3(64 * NW), 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl,
+                           rows.kind, rows.key, h->thr.p, h->thr32.p, h->thr_stride, part, round, mode, h->part_stride, srank, sworld,
+                           h->pstat_p(), (const int*)nullptr, gF, found, (const unsigned*)h->masks.p, h->mask_stride, tps, q);
+    }
+};
 
 template <int DP, bool DIRTY>
 void launch_scan_dp(cc_handle* h, hipStream_t st, int win, Rows rows, const Cand* clean, Cand* part, int S, int round,
@@ -640,232 +808,115 @@ void launch_scan_dp(cc_handle* h, hipStream_t st, int win, Rows rows, const Cand
     const dim3 block(64 * NW);
     constexpr int TILE = 64 * ScanShape<DP, DIRTY>::PT;  // window points per workgroup
     const dim3 grid((win + TILE - 1) / TILE, S);
-    // the clean scan is compiled without the pdim filter for the common case pi >= d; the dirty scan (few rows
-    // survive its pruning) tests the flag at run time
-    const bool filter = DIRTY || h->hc.filter != 0;
-#define CC_LAUNCH_SCAN(F, P)                                                                                   \
-    hipLaunchKernelGGL((k_scan<DP, F, P, DIRTY, NW>), grid, block, 0, st, h->ctl.p, h->X.p, h->Xt.p, rows, clean, \
-                       part, round, mode, h->part_stride, shard_rank, shard_world)
     if constexpr (!DIRTY) {
-        // the common case (k a power of two, no pdim filter, no padded dimensions): rows as scalar operands
         static_assert(ScanShape<DP, false>::PT == 1, "k_scan_u holds one window point per lane");
-        if (scan_u_applies(h, DP)) {
-            ++h->stats.scan_u_launches;
-            if constexpr (DP > 8) {
-                // prefix scores -> thresholds -> the scan that abandons rows whose partial sums pass them; for the
-                // window's points (plist == nullptr) or for the ones a guessed threshold missed
-                // k_scan_p for the window's points: phase A as a kernel of its own (two points per lane, survivor masks), phase
-                // B behind it; lists of points (the ones a guessed threshold missed, probes) keep the one-kernel form
-                auto scan_p_window = [&](int srank, int sworld, double gF, unsigned long long* found_, bool have_prefix16 = false) {
-                    const bool one_kernel = h->split_a_mode == 0 || (h->split_a_mode == 1 && h->hc.m_rows < 10000);
-                    if (one_kernel || (h->allow_scan_p3 && h->split_a_mode == 1 && DP <= 40)) {
-                        if constexpr (DP <= 40) {
-                            // one kernel, phase A on the matrix cores (cc_scan16.h): the rows as half-precision operands first
-                            // (at any table size: CHRONOCLUST_HIP_SCANA=2 keeps the two-kernel form of large tables)
-                            if (h->allow_scan_p3) {
-                                ensure_prefix16(h);
-                                const size_t a16_rows = h->tab.cap + 2 * CC_P16_TM;
-                                if (!have_prefix16)
-                                    hipLaunchKernelGGL((k_prefix16<DP>), dim3((unsigned)((a16_rows + 255) / 256)), dim3(256), 0, st, (const Ctl*)h->ctl.p,
-                                                       rows.cen, rows.kind, h->a16.p, h->hdr16.p, h->a16_stride, round, mode);
-                                // (unused dynamic LDS caps the workgroups a CU holds: CHRONOCLUST_HIP_SCAN_LDS_KB, an experiment knob)
-                                static const unsigned p3_lds = []() { const char* e = getenv("CHRONOCLUST_HIP_SCAN_LDS_KB"); return e ? (unsigned)atoi(e) * 1024u : 0u; }();
-                                // (kept rows listed per wave and walked with their operands prefetched - LISTED - from p3_listed_rows table rows on)
-                                if (h->hc.m_rows >= h->p3_listed_rows)
-                                    hipLaunchKernelGGL((k_scan_p3<DP, NW, true, false>), dim3((win + 127) / 128, S), block, p3_lds, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl,
-                                                       rows.kind, rows.key, h->thr.p, h->thr_stride, part, round, mode, h->part_stride, srank, sworld,
-                                                       h->pstat_p(), gF, found_, (const cc_h8*)h->a16.p, (const Prefix16Hdr*)h->hdr16.p, h->a16_stride,
-                                                       (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr);
-                                else
-                                    hipLaunchKernelGGL((k_scan_p3<DP, NW, false, false>), dim3((win + 127) / 128, S), block, p3_lds, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl,
-                                                       rows.kind, rows.key, h->thr.p, h->thr_stride, part, round, mode, h->part_stride, srank, sworld,
-                                                       h->pstat_p(), gF, found_, (const cc_h8*)h->a16.p, (const Prefix16Hdr*)h->hdr16.p, h->a16_stride,
-                                                       (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr);
-                                ++h->stats.scan_p2_launches;
-                                return;
-                            }
-                            // one kernel, two points per lane in phase A, phase B from the same residency (k_scan_p2)
-                            if (h->allow_scan_p2) {
-                                hipLaunchKernelGGL((k_scan_p2<DP, NW>), dim3((win + 127) / 128, S), block, 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl,
-                                                   rows.kind, rows.key, h->thr.p, h->thr_stride, part, round, mode, h->part_stride, srank, sworld,
-                                                   h->pstat_p(), gF, found_);
-                                ++h->stats.scan_p2_launches;
-                                return;
-                            }
-                        }
-                        hipLaunchKernelGGL((k_scan_p<DP, NW, false>), grid, block, 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl, rows.kind,
-                                           rows.key, h->thr.p, h->thr32.p, h->thr_stride, part, round, mode, h->part_stride, srank, sworld,
-                                           h->pstat_p(), (const int*)nullptr, gF, found_, (const unsigned*)nullptr, (size_t)0, 0, 1);
-                        return;
-                    }
-                    const int nsub = S * NW;
-                    const int tps = cc_mask_tiles_per_sub((int)std::min<size_t>(h->tab.cap, (size_t)INT_MAX - 64), nsub);
-                    const size_t need = (size_t)((win + 127) / 128) * (size_t)nsub * (size_t)tps;
-                    if (need > h->mask_stride) {
-                        h->masks.ensure(2 * need);
-                        h->mask_stride = need;
-                    }
-                    hipLaunchKernelGGL((k_scan_a<DP, NW>), dim3((win + 127) / 128, S), block, 0, st, (const Ctl*)h->ctl.p,
-                                       (const double*)h->Xt.p, rows.cen, rows.kind, (const double*)h->thr.p, h->thr_stride,
-                                       h->masks.p, h->mask_stride, tps, round, mode, srank, sworld, gF);
-                    // phase B: about one and a half rounds of the resident workgroups, i.e. q of phase A's sub-ranges per wave
-                    // (its waves live on chains of memory round trips - prologue, masks, a few rows, merge -, not on arithmetic:
-                    // with phase A's own split - eight rounds at the C5 shape - the prologues dominate, with one round every
-                    // wave walks q times the rows; 2 M x 40, 50 000 rows: q = 1 / 2 / 3 / 4 / 6 / 12 -> 39.6 / 40.6 / 40.7 /
-                    // 41.2 / 39.9 / 39.8 M points/s.  CHRONOCLUST_HIP_SCANB_Q overrides.)
-                    int q = 1;
-                    {
-                        const int tiles = (win + 63) / 64;
-                        const int resident = h->n_cus * (DP <= 20 ? CC_SCANP_WGS20 : (DP <= 40 ? 3 : 2));
-                        for (int c = 1; c <= S; ++c)
-                            if (S % c == 0 && 2 * tiles * (S / c) >= 3 * resident) q = c;
-                        static const int q_env = []() { const char* e = getenv("CHRONOCLUST_HIP_SCANB_Q"); return e ? atoi(e) : 0; }();
-                        if (q_env > 0 && S % q_env == 0) q = q_env;
-                    }
-                    hipLaunchKernelGGL((k_scan_p<DP, NW, true>), dim3(grid.x, S / q), block, 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl,
-                                       rows.kind, rows.key, h->thr.p, h->thr32.p, h->thr_stride, part, round, mode, h->part_stride, srank,
-                                       sworld, h->pstat_p(), (const int*)nullptr, gF, found_, (const unsigned*)h->masks.p,
-                                       h->mask_stride, tps, q);
-                };
-                auto seeded_chain = [&](int n_pts, const int* plist, Cand* part, size_t part_stride, int S) {
-                        const bool whole_window = plist == nullptr && n_pts == win && part_stride == h->part_stride && S == (int)grid.y;
-                        // seeds from the matrix cores and the tight threshold they allow (k_seed16; round 6) where the window's scan is
-                        // k_scan_p3: the rows' half-precision records first, they serve both kernels
-                        bool s16 = false;
-                        if constexpr (DP <= 40) s16 = whole_window && h->allow_seed16 && h->allow_scan_p3 && h->split_a_mode != 2;
-                        if (s16) {
-                            if constexpr (DP <= 40) {
-                                ensure_prefix16(h);
-                                const size_t a16_rows = h->tab.cap + 2 * CC_P16_TM;
-                                hipLaunchKernelGGL((k_prefix16<DP>), dim3((unsigned)((a16_rows + 255) / 256)), dim3(256), 0, st, (const Ctl*)h->ctl.p,
-                                                   rows.cen, rows.kind, h->a16.p, h->hdr16.p, h->a16_stride, round, mode);
-                                hipLaunchKernelGGL((k_seed16<DP, NW>), dim3((n_pts + 127) / 128, S), block, 0, st, (const Ctl*)h->ctl.p, (const double*)h->Xt.p,
-                                                   rows.cen, h->spart.p, round, mode, h->spart_stride, (const cc_h8*)h->a16.p,
-                                                   (const Prefix16Hdr*)h->hdr16.p, h->a16_stride);
-                                ++h->stats.seed16_launches;
-                            }
+        const ScanPlan& pl = h->scan_plan;
+        const ScanCall<DP> L{h, st, rows, round, mode, win, S, part};
+        if (pl.scan_u) ++h->stats.scan_u_launches;  // (every window where k_scan_u applies, pruned or not)
+        if constexpr (DP > 8) {
+            // prefix scores -> thresholds -> the scan that abandons rows whose partial sums pass them.  The window's pruned
+            // scan, against guessed thresholds (gF > 0; `found`: who found a pcore MC, per point tile) or seeded ones:
+            auto window_scan = [&](int srank, int sworld, double gF, unsigned long long* found, bool have_prefix16) {
+                if (pl.split(h->hc.m_rows)) return L.scan_split(srank, sworld, gF, found);
+                if constexpr (DP <= 40) {
+                    if (pl.form == ScanPlan::P3) {
+                        if (!have_prefix16) L.prefix16();
+                        // (LISTED: the kept rows listed per wave and walked with their operands prefetched)
+                        const bool listed = pl.listed(h->hc.m_rows);
+                        if (pl.chain == ScanPlan::GENERAL) {
+                            if (listed) L.template scan_p3<true, true>(0, srank, sworld, gF, found);
+                            else L.template scan_p3<false, true>(0, srank, sworld, gF, found);
                         } else {
-                            // (k_seed holds two points per lane: point tiles of 128)
-                            hipLaunchKernelGGL((k_seed<DP, NW>), dim3((n_pts + 127) / 128, S), block, 0, st, h->ctl.p, h->Xt.p, rows.cen,
-                                               rows.kind, h->spart.p, round, mode, h->spart_stride, h->cmax.p, plist);
+                            // (unused dynamic LDS caps the workgroups a CU holds: CHRONOCLUST_HIP_SCAN_LDS_KB, an experiment knob)
+                            static const char* const lds_kb = getenv("CHRONOCLUST_HIP_SCAN_LDS_KB");
+                            static const unsigned p3_lds = lds_kb ? (unsigned)atoi(lds_kb) * 1024u : 0u;
+                            if (listed) L.template scan_p3<true, false>(p3_lds, srank, sworld, gF, found);
+                            else L.template scan_p3<false, false>(p3_lds, srank, sworld, gF, found);
                         }
-                        hipLaunchKernelGGL((k_seed_merge<DP>), dim3((2 * n_pts + 63) / 64), dim3(64), 0, st, h->ctl.p, h->X.p, rows.cen,
-                                           rows.scl, h->spart.p, h->spart_stride, S, h->thr.p, h->thr32.p, h->thr_stride,
-                                           s16 ? 0.0 : h->prune_F, round, mode, h->cmax.p, h->pstat_p(), plist);
-                        // (split over the ranks of a group: seeds and thresholds over ALL rows on every rank - replicated, so
-                        // that every rank abandons against the same T -, phases A / B over the rank's own rows)
-                        if (whole_window) {
-                            scan_p_window(shard_rank, shard_world, 0.0, (unsigned long long*)nullptr, s16);
-                            return;
-                        }
-                        hipLaunchKernelGGL((k_scan_p<DP, NW, false>), dim3((n_pts + 63) / 64, S), block, 0, st, h->ctl.p, h->Xt.p, rows.cen,
-                                           rows.scl, rows.kind, rows.key, h->thr.p, h->thr32.p, h->thr_stride, part, round, mode,
-                                           part_stride, shard_rank, shard_world, h->pstat_p(), plist, 0.0,
-                                           (unsigned long long*)nullptr, (const unsigned*)nullptr, (size_t)0, 0, 1);
-                };
-                // the points a guessed threshold missed: the plain scan over their list (k_scan_u's header says why); the seeded
-                // chain on request (CHRONOCLUST_HIP_MISSED_PLAIN=0)
-                auto missed_scan = [&](const int* list) {
-                    if (!h->allow_missed_plain) {
-                        seeded_chain(CC_MISSED_CAP, list, part, h->part_stride, S);
+                        ++h->stats.scan_p2_launches;
                         return;
                     }
-                    ++h->stats.missed_plain_launches;
-                    hipLaunchKernelGGL((k_scan_u<DP, NW>), dim3((CC_MISSED_CAP + 63) / 64, S), block, 0, st, h->ctl.p, h->Xt.p, rows.cen,
-                                       rows.scl, rows.kind, rows.key, part, round, mode, h->part_stride, shard_rank, shard_world, list);
-                };
+                    if (pl.form == ScanPlan::P2) {  // (one kernel, two points per lane in phase A, phase B from the same residency)
+                        hipLaunchKernelGGL((k_scan_p2<DP, NW>), dim3((win + 127) / 128, S), block, 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl,
+                                           rows.kind, rows.key, h->thr.p, h->thr_stride, part, round, mode, h->part_stride, srank, sworld,
+                                           h->pstat_p(), gF, found);
+                        ++h->stats.scan_p2_launches;
+                        return;
+                    }
+                }
+                L.scan_p(win, S, part, h->part_stride, srank, sworld, nullptr, gF, found);
+            };
+            // seeds and thresholds, then the pruned scan, for n_pts points of the window or a list (plist), Sp partials per point
+            // into p.  (Split over the ranks of a group: seeds and thresholds over ALL rows on every rank - replicated, so that
+            // every rank abandons against the same T -, phases A / B over the rank's own rows.)
+            auto seeded_chain = [&](int n_pts, const int* plist, Cand* p, size_t p_stride, int Sp, int srank, int sworld) {
+                const bool whole_window = plist == nullptr && n_pts == win && p_stride == h->part_stride && Sp == S;
+                // (the rows' half-precision records first where k_seed16 or GENERAL's k_scan_p3 read them: they serve both)
+                const bool s16 = whole_window && pl.seed16;
+                const bool have_prefix16 = whole_window && (s16 || pl.chain == ScanPlan::GENERAL);
+                if constexpr (DP <= 40) if (have_prefix16) L.prefix16();
+                L.seeds(n_pts, Sp, plist, s16);
+                if (whole_window) window_scan(srank, sworld, 0.0, nullptr, have_prefix16);
+                else L.scan_p(n_pts, Sp, p, p_stride, srank, sworld, plist, 0.0, nullptr);
+            };
+            // the points a guessed threshold missed: the plain scan over their list (k_scan_u's header says why); the seeded
+            // chain on request (CHRONOCLUST_HIP_MISSED_PLAIN=0)
+            auto missed_scan = [&](const int* list) {
+                if (!h->allow_missed_plain) return seeded_chain(CC_MISSED_CAP, list, part, h->part_stride, S, shard_rank, shard_world);
+                ++h->stats.missed_plain_launches;
+                L.scan_u(CC_MISSED_CAP, shard_rank, shard_world, list);
+            };
+            if (pl.chain == ScanPlan::GENERAL && h->prune_now && phase == 0) {
+                ++h->stats.scan_p_launches;
+                return seeded_chain(win, nullptr, part, h->part_stride, S, shard_rank, shard_world);
+            }
+            if (pl.chain == ScanPlan::COMMON) {
                 if (phase == 1) {
                     // guessed thresholds on the exact multi-GPU path, after the ranks' records were gathered: the points
                     // whose merged pcore list starts with a bound (k_missed_g: the same list on every rank) go through the
                     // seeded chain - seeds over all rows on every rank, phases A / B over the rank's rows
                     hipLaunchKernelGGL(k_missed_g, dim3(1), dim3(1024), 0, st, h->ctl.p, (const Cand*)h->gpart.p, h->gpart_stride,
                                        (size_t)win * 4 + 4, shard_world, h->missed.p, CC_MISSED_CAP, round, mode, h->found.p);
-                    missed_scan(h->missed.p);
-                    return;
+                    return missed_scan(h->missed.p);
                 }
-                if (h->prune_now) {
-                    ++h->stats.scan_p_launches;
-                    if (h->guess_now && h->group_guess_now) {
-                        // (split over ranks: every rank scans its rows against the same guess; who was missed is only known
-                        // once the records are gathered - phase 1, enqueued by the caller behind the all-gather)
-                        ++h->stats.scan_g_launches;
-                        hipLaunchKernelGGL(k_pstat_zero, dim3(1), dim3(2), 0, st, (const Ctl*)h->ctl.p, h->pstat_p(), round, mode);
-                        scan_p_window(shard_rank, shard_world, h->prune_F, h->lean_now ? (unsigned long long*)nullptr : h->found.p);
-                        return;
-                    }
-                    if (h->guess_now) {
-                        // guessed thresholds: one scan, the list of the points it missed, the seeded chain for those
-                        // (list of the window's parity: the lookahead scan of the next window fills the other one)
-                        ++h->stats.scan_g_launches;
-                        int* const list = h->missed.p;  // (the kernels take the half of the window's parity)
-                        scan_p_window(0, 1, h->prune_F, h->lean_now ? (unsigned long long*)nullptr : h->found.p);
-                        if (h->lean_now) {  // (nobody is expected to be missed: see cc_policy.h)
-                            ++h->stats.scan_lean_launches;
-                            return;
-                        }
-                        hipLaunchKernelGGL(k_missed, dim3(1), dim3(1024), 0, st, h->ctl.p, h->found.p, list, CC_MISSED_CAP, round, mode);
-                        missed_scan(list);
-                        return;
-                    }
-                    seeded_chain(win, nullptr, part, h->part_stride, S);
-                    return;
-                }
-                hipLaunchKernelGGL((k_scan_u<DP, NW>), grid, block, 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl, rows.kind,
-                                   rows.key, part, round, mode, h->part_stride, shard_rank, shard_world);
-                if (h->probe_now) {
-                    // the probe: the pruned chain on the window's first 128 points, over all rows, into scratch partials -
-                    // only its sample of completed rows (Ctl::stat_prune_*) is used, by the window policy
+                if (!h->prune_now) {
+                    L.scan_u(win, shard_rank, shard_world, nullptr);
+                    if (!h->probe_now) return;
+                    // the probe: the pruned chain on the window's first 128 points, over all rows (the whole table on every
+                    // rank: the same sample everywhere), into scratch partials - only its sample of completed rows
+                    // (Ctl::stat_prune_*) is used, by the window policy.  (Few points, so many sub-ranges of rows: while the
+                    // table fills most rows are completed, at the latency of scalar loads - 128 workgroups per point tile keep
+                    // that to a hundred rows per wave.)
                     ++h->stats.probe_launches;
-                    const int keep_rank = shard_rank, keep_world = shard_world;
-                    shard_rank = 0; shard_world = 1;  // (the whole table on every rank: the same sample everywhere)
-                    // (few points, so many sub-ranges of rows: while the table fills most rows are completed, at the
-                    // latency of scalar loads - 128 workgroups per point tile keep that to a hundred rows per wave)
                     const int Sp = (int)std::max<size_t>(1, std::min<size_t>(128, h->spart_stride / 2 / 128));  // (what the seed buffer holds for 128 points)
                     h->probe_part.ensure((size_t)2 * 128 * Sp * 4);
-                    seeded_chain(std::min(win, 128), nullptr, h->probe_part.p, (size_t)128 * Sp * 4, Sp);
-                    shard_rank = keep_rank; shard_world = keep_world;
+                    return seeded_chain(std::min(win, 128), nullptr, h->probe_part.p, (size_t)128 * Sp * 4, Sp, 0, 1);
                 }
-                return;
+                ++h->stats.scan_p_launches;
+                if (!h->guess_now) return seeded_chain(win, nullptr, part, h->part_stride, S, shard_rank, shard_world);
+                ++h->stats.scan_g_launches;
+                unsigned long long* const found = h->lean_now ? nullptr : h->found.p;
+                if (h->group_guess_now) {
+                    // (split over ranks: every rank scans its rows against the same guess; who was missed is only known
+                    // once the records are gathered - phase 1, enqueued by the caller behind the all-gather)
+                    hipLaunchKernelGGL(k_pstat_zero, dim3(1), dim3(2), 0, st, (const Ctl*)h->ctl.p, h->pstat_p(), round, mode);
+                    return window_scan(shard_rank, shard_world, h->prune_F, found, false);
+                }
+                // guessed thresholds: one scan, the list of the points it missed, the seeded chain for those (list of the
+                // window's parity - the kernels take that half -: the lookahead scan of the next window fills the other one)
+                window_scan(0, 1, h->prune_F, found, false);
+                if (h->lean_now) { ++h->stats.scan_lean_launches; return; }  // (nobody is expected to be missed: see cc_policy.h)
+                hipLaunchKernelGGL(k_missed, dim3(1), dim3(1024), 0, st, h->ctl.p, h->found.p, h->missed.p, CC_MISSED_CAP, round, mode);
+                return missed_scan(h->missed.p);
             }
-            hipLaunchKernelGGL((k_scan_u<DP, NW>), grid, block, 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.scl, rows.kind,
-                               rows.key, part, round, mode, h->part_stride, shard_rank, shard_world);
-            return;
         }
+        if (pl.scan_u) return L.scan_u(win, shard_rank, shard_world, nullptr);
     }
-    if constexpr (!DIRTY && DP > 8 && DP <= 40) {
-        // the pruned chain where the pdim filter is on or k is not a power of two (round 6): seeds and thresholds as ever (any
-        // threshold is a valid one), then k_scan_p3<GENERAL>.  Seeded thresholds only: the points a guessed threshold misses
-        // would need a plain scan over a point list, which exists for the common case alone (k_scan_u).
-        if (h->prune_now && scan_p3_general_applies(h, DP) && phase == 0) {
-            ++h->stats.scan_p_launches;
-            ++h->stats.scan_p2_launches;
-            ensure_prefix16(h);
-            const size_t a16_rows = h->tab.cap + 2 * CC_P16_TM;
-            hipLaunchKernelGGL((k_prefix16<DP>), dim3((unsigned)((a16_rows + 255) / 256)), dim3(256), 0, st, (const Ctl*)h->ctl.p, rows.cen,
-                               rows.kind, h->a16.p, h->hdr16.p, h->a16_stride, round, mode);
-            if (h->allow_seed16) {
-                hipLaunchKernelGGL((k_seed16<DP, NW>), dim3((win + 127) / 128, S), block, 0, st, (const Ctl*)h->ctl.p, (const double*)h->Xt.p, rows.cen,
-                                   h->spart.p, round, mode, h->spart_stride, (const cc_h8*)h->a16.p, (const Prefix16Hdr*)h->hdr16.p, h->a16_stride);
-                ++h->stats.seed16_launches;
-            } else
-                hipLaunchKernelGGL((k_seed<DP, NW>), dim3((win + 127) / 128, S), block, 0, st, h->ctl.p, h->Xt.p, rows.cen, rows.kind,
-                                   h->spart.p, round, mode, h->spart_stride, h->cmax.p, (const int*)nullptr);
-            hipLaunchKernelGGL((k_seed_merge<DP>), dim3((2 * win + 63) / 64), dim3(64), 0, st, h->ctl.p, h->X.p, rows.cen, rows.scl,
-                               h->spart.p, h->spart_stride, S, h->thr.p, h->thr32.p, h->thr_stride, h->allow_seed16 ? 0.0 : h->prune_F, round,
-                               mode, h->cmax.p, h->pstat_p(), (const int*)nullptr);
-            if (h->hc.m_rows >= h->p3_listed_rows)
-                hipLaunchKernelGGL((k_scan_p3<DP, NW, true, true>), dim3((win + 127) / 128, S), block, 0, st, h->ctl.p, h->Xt.p, rows.cen,
-                                   rows.scl, rows.kind, rows.key, h->thr.p, h->thr_stride, part, round, mode, h->part_stride, shard_rank,
-                                   shard_world, h->pstat_p(), 0.0, (unsigned long long*)nullptr, (const cc_h8*)h->a16.p,
-                                   (const Prefix16Hdr*)h->hdr16.p, h->a16_stride, (const double*)h->X.p, rows.cf1, rows.cf2, rows.w);
-            else
-                hipLaunchKernelGGL((k_scan_p3<DP, NW, false, true>), dim3((win + 127) / 128, S), block, 0, st, h->ctl.p, h->Xt.p, rows.cen,
-                                   rows.scl, rows.kind, rows.key, h->thr.p, h->thr_stride, part, round, mode, h->part_stride, shard_rank,
-                                   shard_world, h->pstat_p(), 0.0, (unsigned long long*)nullptr, (const cc_h8*)h->a16.p,
-                                   (const Prefix16Hdr*)h->hdr16.p, h->a16_stride, (const double*)h->X.p, rows.cf1, rows.cf2, rows.w);
-            return;
-        }
-    }
+    // k_scan: the clean scan is compiled without the pdim filter for the common case pi >= d; the dirty scan (few rows
+    // survive its pruning) tests the flag at run time
+    const bool filter = DIRTY || h->hc.filter != 0;
+#define CC_LAUNCH_SCAN(F, P) hipLaunchKernelGGL((k_scan<DP, F, P, DIRTY, NW>), grid, block, 0, st, h->ctl.p, h->X.p, h->Xt.p, rows, clean, \
+                                          part, round, mode, h->part_stride, shard_rank, shard_world)
     if (filter) {
         if (h->hc.pow2) CC_LAUNCH_SCAN(true, true);
         else CC_LAUNCH_SCAN(true, false);
@@ -883,55 +934,19 @@ template <bool DIRTY>
 void launch_scan(cc_handle* h, hipStream_t st, int win, Rows rows, const Cand* clean, Cand* part, int S, int round,
                  int mode, int shard_rank = 0, int shard_world = 1, int phase = 0)
 {
-    const int d = h->d;
-#define CC_SCAN_DP(DP) launch_scan_dp<DP, DIRTY>(h, st, win, rows, clean, part, S, round, mode, shard_rank, shard_world, phase)
-    // (padded dimensions cost full distance terms: the ladder follows the shapes of BASELINE.json - d = 14, 20, 40)
-    if (d <= 4) CC_SCAN_DP(4);
-    else if (d <= 8) CC_SCAN_DP(8);
-    else if (d <= 14) CC_SCAN_DP(14);
-    else if (d <= 16) CC_SCAN_DP(16);
-    else if (d <= 20) CC_SCAN_DP(20);
-    else if (d <= 32) CC_SCAN_DP(32);
-    else if (d <= 40) CC_SCAN_DP(40);
-    else CC_SCAN_DP(64);
+#define CC_SCAN_DP(DP) return launch_scan_dp<DP, DIRTY>(h, st, win, rows, clean, part, S, round, mode, shard_rank, shard_world, phase)
+    switch (h->scan_plan.dp) {
+    case 4: CC_SCAN_DP(4);
+    case 8: CC_SCAN_DP(8);
+    case 14: CC_SCAN_DP(14);
+    case 16: CC_SCAN_DP(16);
+    case 20: CC_SCAN_DP(20);
+    case 32: CC_SCAN_DP(32);
+    case 40: CC_SCAN_DP(40);
+    case 64: CC_SCAN_DP(64);
+    }
+    throw HipErr{hipErrorInvalidValue, "launch_scan before scan_plan() (OnlineRun::prepare)"};
 #undef CC_SCAN_DP
-}
-
-// workgroups of the clean scan that are resident at once (compute units x workgroups per CU it is compiled for)
-template <int DP>
-int scan_u_wgs_per_cu()
-{
-    static const int n = []() {
-        int blocks = 0;
-        constexpr int NW = ScanShape<DP, false>::NW;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_scan_u<DP, NW>, 64 * NW, 0) != hipSuccess || blocks < 1)
-            blocks = ScanUShape<DP>::WGS;
-        return blocks;
-    }();
-    return n;
-}
-
-int scan_resident_wgs(const cc_handle* h, int n_cus)
-{
-    const int d = h->d;
-    if (d == 4 && scan_u_applies(h, 4)) return n_cus * scan_u_wgs_per_cu<4>();
-    if (d == 8 && scan_u_applies(h, 8)) return n_cus * scan_u_wgs_per_cu<8>();
-    if (d == 14 && scan_u_applies(h, 14)) return n_cus * scan_u_wgs_per_cu<14>();
-    if (d == 16 && scan_u_applies(h, 16)) return n_cus * scan_u_wgs_per_cu<16>();
-    if (d == 20 && scan_u_applies(h, 20)) return n_cus * scan_u_wgs_per_cu<20>();
-    if (d == 32 && scan_u_applies(h, 32)) return n_cus * scan_u_wgs_per_cu<32>();
-    if (d == 40 && scan_u_applies(h, 40)) return n_cus * scan_u_wgs_per_cu<40>();
-    if (d == 64 && scan_u_applies(h, 64)) return n_cus * scan_u_wgs_per_cu<64>();
-    int per_cu;
-    if (d <= 4) per_cu = ScanShape<4, false>::WGS;
-    else if (d <= 8) per_cu = ScanShape<8, false>::WGS;
-    else if (d <= 14) per_cu = ScanShape<14, false>::WGS;
-    else if (d <= 16) per_cu = ScanShape<16, false>::WGS;
-    else if (d <= 20) per_cu = ScanShape<20, false>::WGS;
-    else if (d <= 32) per_cu = ScanShape<32, false>::WGS;
-    else if (d <= 40) per_cu = ScanShape<40, false>::WGS;
-    else per_cu = ScanShape<64, false>::WGS;
-    return n_cus * per_cu;
 }
 
 // Partials per point for a batch whose windows have `tiles` point tiles: at most S, not less than S / 2, chosen so that
@@ -947,13 +962,6 @@ int scan_partials_for(int tiles, int S, int resident)
         if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
     }
     return best;
-}
-
-// waves per workgroup of the scans at dimensionality d (the host turns `segments` sub-ranges into partials per point)
-int scan_waves_for_dim(int d, bool dirty)
-{
-    if (dirty) return 4;
-    return (d > 16 && d <= 20) ? ScanShape<20, false>::NW : 4;
 }
 
 hipEvent_t get_event(cc_handle* h, size_t i)
@@ -1733,11 +1741,14 @@ struct OnlineRun {
     // buffers, control block, policy: everything before the first batch
     void prepare()
     {
+        refresh_ctl_params(h);
+        // how this call's snapshot scans run (the pdim filter and k are fixed for the call)
+        h->scan_plan = scan_plan(h);
+        const ScanPlan& plan = h->scan_plan;
         win = h->tun.window; R = h->tun.rounds;
-        // `segments` MC sub-ranges per point tile = S workgroups of 4 waves -> S partials per point
-        S_cfg = std::max(1, h->tun.segments / scan_waves_for_dim(h->d, false));
-        Sd_full = std::max(1, (h->tun.dirty_segments > 0 ? h->tun.dirty_segments : h->tun.segments) /
-                                            scan_waves_for_dim(h->d, true));
+        // `segments` MC sub-ranges per point tile = S workgroups of `waves` waves -> S partials per point
+        S_cfg = std::max(1, h->tun.segments / plan.waves);
+        Sd_full = std::max(1, (h->tun.dirty_segments > 0 ? h->tun.dirty_segments : h->tun.segments) / plan.dirty_waves);
         // while the dirty scans are ruled out tile by tile (k_dseed) their launches only have to be scheduled: a
         // few workgroups per point tile then, the full split while they really run (set per batch below)
         Sd = Sd_full;
@@ -1746,7 +1757,6 @@ struct OnlineRun {
         // workgroup); k_decide then refuses points that would have needed them, the device idles the rest of the batch
         // if that stops a window at its first point, and the next batch launches them again.
         nodirty = false;
-        refresh_ctl_params(h);
         ensure_window_buffers(h, win, std::max(S_cfg, Sd_full));
         // Exact multi-GPU path: while the table is large enough, every rank scans its share of the table rows and
         // the ranks all-gather one merged candidate record per window point; the rest of the window runs replicated.
@@ -1783,19 +1793,15 @@ struct OnlineRun {
         pcfg.lookahead = h->tun.lookahead;
         pcfg.allow_nodirty = h->allow_nodirty ? 1 : 0;
         pcfg.prune_mode = h->prune_mode;
-        const bool width_ok = h->d == 14 || h->d == 16 || h->d == 20 || h->d == 32 || h->d == 40;
-        // (the pdim filter on and / or k not a power of two: k_scan_p3<GENERAL> behind seeded thresholds - no guesses, no probes)
-        const bool prune_general = width_ok && scan_p3_general_applies(h, h->d);
-        pcfg.prune_applicable = ((h->d > 8 && h->allow_scan_u && h->hc.filter == 0 && h->hc.pow2 != 0 && (width_ok || h->d == 64)) || prune_general) ? 1 : 0;
+        pcfg.prune_applicable = plan.prune_applicable;
         pcfg.can_shard = (grouped && !h->shard_suspended) ? 1 : 0;
         pcfg.d = h->d;
         pcfg.resume = resume ? 1 : 0;
         pcfg.allow_sparse = h->allow_sparse;
-        pcfg.allow_guess = (h->allow_guess && !prune_general) ? (h->allow_lean ? 1 : 2) : 0;  // (2: guessed thresholds, never lean)
-        pcfg.allow_probe = (h->allow_probe && !prune_general) ? 1 : 0;
+        pcfg.allow_guess = plan.allow_guess;
+        pcfg.allow_probe = plan.allow_probe;
         pcfg.lookahead_pruned = h->la_pruned ? 1 : 0;
-        // (pruned scans from this many rows on whatever the phase: where the seeded chain runs behind k_seed16)
-        pcfg.force_prune_rows = (pcfg.prune_applicable && h->allow_seed16 && h->allow_scan_p3 && h->d <= 40 && h->split_a_mode != 2) ? h->force_prune_rows : 0;
+        pcfg.force_prune_rows = plan.force_prune_rows;
         pcfg.shard_min_row_dims = h->shard_min_row_dims;
         pcfg.shard_min_row_dims_pruned = h->shard_min_row_dims_pruned;
         pcfg.n_end = N;
@@ -1994,15 +2000,9 @@ struct OnlineRun {
         // (points, thresholds, tile pipeline, candidate merge: microseconds) not to dominate: as few sub-ranges as fill
         // the machine once (about a fifth of the plain scan's partials at the full window).
         const int scan_cus = h->n_cus;
-        // (measured, `profiles/r03_tool_prune_split.txt`: four rounds of the resident workgroups at d <= 20 - k_scan_p is
-        // compiled for four per CU there -, eight of the three per CU beyond)
-        // (round 6, k_scan_p3: the prefix test costs next to nothing on the matrix cores, what is left of a workgroup's time is its
-        // prologue - the points staged, their constants - and the rows it completes: two rounds of the resident workgroups at
-        // d <= 20, 54 against 63 us per C2 window running alone, half the partials per point)
-        const bool p3 = h->allow_scan_p3 && h->d <= 40 && h->split_a_mode != 2;
-        const int prune_wgs = h->prune_rounds4 > 0 ? h->prune_rounds4 : (h->d <= 20 ? (p3 ? 8 : 16) : 24);
-        const int S = h->prune_now ? std::max(1, std::min(S_cfg, (scan_cus * prune_wgs) / std::max(1, (gw + 63) / 64)))
-                                   : scan_partials_for((gw + 63) / 64, S_cfg, scan_resident_wgs(h, scan_cus));
+        const ScanPlan& plan = h->scan_plan;
+        const int S = h->prune_now ? std::max(1, std::min(S_cfg, (scan_cus * plan.prune_wgs_per_cu) / std::max(1, (gw + 63) / 64)))
+                                   : scan_partials_for((gw + 63) / 64, S_cfg, scan_cus * plan.plain_wgs_per_cu);
         // capacity of the round's list for the sparse dirty scans: a sixteenth of the window (the policy's bound on
         // the batch's average), in whole tiles
         const int sparse_cap = std::min(CC_MAX_WINDOW / 16, std::max(64, ((gw / 16 + 63) / 64) * 64));
