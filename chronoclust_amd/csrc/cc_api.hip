@@ -409,6 +409,11 @@ struct PolicyTrace {
     PolicyTrace& operator=(const PolicyTrace&) = delete;
 };
 
+// a device buffer the library refuses to size (ensure_table): CC_ERR_OOM with the reason
+struct CapacityErr {
+    std::string what;
+};
+
 int fail(cc_handle* h, int code, const std::string& msg)
 {
     if (h) h->err = msg;
@@ -442,6 +447,9 @@ int guarded(cc_handle* h, F&& f)
     } catch (const std::bad_alloc&) {
         group_lost(h);
         return fail(h, CC_ERR_OOM, "host allocation failed");
+    } catch (const CapacityErr& e) {
+        group_lost(h);
+        return fail(h, CC_ERR_OOM, e.what);
     }
 }
 
@@ -511,11 +519,19 @@ void push_ctl_pinned(cc_handle* h)
     HIPCHK(hipMemcpyAsync(h->ctl.p, h->hc_pin + 1, sizeof(Ctl), hipMemcpyHostToDevice, h->stream));
 }
 
+// The kernels over the table index its elements with an int (row * d + dimension, up to a block of threads past the end):
+// a capacity of more than CC_MAX_TABLE_ELEMS / d rows is refused rather than overflowed (2 M rows at d = 1 024).
+#define CC_MAX_TABLE_ELEMS ((size_t)INT_MAX - 1023)
+
 // grow the table to at least `rows` rows, keeping the first m_rows rows
 void ensure_table(cc_handle* h, size_t rows)
 {
     if (h->tab.cap >= rows && h->tab.d == h->d) return;
-    size_t want = std::max<size_t>(rows, std::max<size_t>(1024, h->tab.cap * 2));
+    const size_t max_rows = CC_MAX_TABLE_ELEMS / (size_t)std::max(h->d, 1);
+    if (rows > max_rows)
+        throw CapacityErr{"a table of " + std::to_string(rows) + " rows of " + std::to_string(h->d) + " dimensions: more than " +
+                          std::to_string(max_rows) + " rows (" + std::to_string(CC_MAX_TABLE_ELEMS) + " elements) at this width"};
+    size_t want = std::min(max_rows, std::max<size_t>(rows, std::max<size_t>(1024, h->tab.cap * 2)));
     TableStore nt;
     nt.alloc(want, h->d);
     const size_t m = (size_t)h->hc.m_rows, d = (size_t)h->d;
@@ -1265,14 +1281,19 @@ int cc_points_upload(cc_handle* h, const double* x, int64_t n, int32_t d)
 // x * scale + min_; cc_points_download_unscaled: (resident points - min_) / scale back to the host.
 int cc_col_minmax(cc_handle* h, const double* x, int64_t n, int32_t d, double* out_min, double* out_max)
 {
-    if (!h || !x || n <= 0 || d <= 0 || d > CC_MAX_DIM || !out_min || !out_max) return CC_ERR_BAD_ARG;
+    if (!h || !x || n <= 0 || !out_min || !out_max) return CC_ERR_BAD_ARG;
+    if (d <= 0 || d > CC_MAX_DIM) return fail(h, CC_ERR_BAD_ARG, "d must be in 1.." + std::to_string(CC_MAX_DIM));
     return guarded(h, [&]() {
         h->scr.ensure((size_t)n * d);
         const int chunks = (int)std::min<long long>(1024, (n + 255) / 256);
         h->scr2.ensure((size_t)2 * chunks * d);
         HIPCHK(hipMemcpyAsync(h->scr.p, x, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_col_minmax, dim3(chunks), dim3(256), 0, h->stream, h->scr.p, (long long)n, (int)d, h->scr2.p,
-                           chunks);
+        if (d <= 256)
+            hipLaunchKernelGGL(k_col_minmax<false>, dim3(chunks), dim3(256), 0, h->stream, h->scr.p, (long long)n, (int)d,
+                               h->scr2.p, chunks);
+        else
+            hipLaunchKernelGGL(k_col_minmax<true>, dim3(chunks, (d + 255) / 256), dim3(256), 0, h->stream, h->scr.p,
+                               (long long)n, (int)d, h->scr2.p, chunks);
         std::vector<double> part((size_t)2 * chunks * d);
         HIPCHK(hipMemcpyAsync(part.data(), h->scr2.p, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
         sync_stream(h, h->stream);
@@ -1368,7 +1389,8 @@ static int upload_points(cc_handle* h, const double* x, int64_t n, int32_t d, co
 
 int cc_points_prefetch(cc_handle* h, const double* x, int64_t n, int32_t d, const double* scale, const double* min_)
 {
-    if (!h || !x || n <= 0 || d <= 0 || d > CC_MAX_DIM || ((scale == nullptr) != (min_ == nullptr))) return CC_ERR_BAD_ARG;
+    if (!h || !x || n <= 0 || ((scale == nullptr) != (min_ == nullptr))) return CC_ERR_BAD_ARG;
+    if (d <= 0 || d > CC_MAX_DIM) return fail(h, CC_ERR_BAD_ARG, "d must be in 1.." + std::to_string(CC_MAX_DIM));
     return guarded(h, [&]() {
         prefetch_discard(h);
         cc_handle::Prefetch& pf = h->pf;
@@ -1711,6 +1733,8 @@ struct OnlineRun {
     // d > CC_WINDOW_MAX_DIM: the windowed path (two dimensions per lane of a 32-lane group, 2 d registers per point in the scans)
     // does not take such points; k_seq_g does, from the first one on
     bool wide() const { return h->d > CC_WINDOW_MAX_DIM; }
+    // table rows a batch of windows may create (none beyond CC_WINDOW_MAX_DIM: k_seq_g's chunks are reserved in run())
+    size_t window_rows() const { return wide() ? 0 : (size_t)win * batch_max; }
     bool seq_g_applies() const { return h->allow_seq_g && h->hc.m_rows >= seq_cap; }
     double seq_rate_guess() const { return cc::seq_rate_guess(h->d, h->hc.m_rows, seq_cap, h->allow_seq_r, h->allow_seq_g); }
     // (never in a group - every rank has to take the same path, and wall-clock measurements differ -, never with no_create:
@@ -1757,7 +1781,8 @@ struct OnlineRun {
         // workgroup); k_decide then refuses points that would have needed them, the device idles the rest of the batch
         // if that stops a window at its first point, and the next batch launches them again.
         nodirty = false;
-        ensure_window_buffers(h, win, std::max(S_cfg, Sd_full));
+        // (beyond CC_WINDOW_MAX_DIM no window runs: the window buffers, w d doubles each, are kept at their smallest)
+        ensure_window_buffers(h, wide() ? 64 : win, std::max(S_cfg, Sd_full));
         // Exact multi-GPU path: while the table is large enough, every rank scans its share of the table rows and
         // the ranks all-gather one merged candidate record per window point; the rest of the window runs replicated.
         // All ranks take the same decision: it depends on the row count only, which is the same everywhere.
@@ -1777,7 +1802,7 @@ struct OnlineRun {
         }
         // every window of a batch may create one MC per point: rows for the largest batch that can be enqueued
         batch_max = (size_t)std::max(2, h->tun.windows_per_sync);
-        ensure_table(h, (size_t)h->hc.m_rows + (size_t)win * batch_max + 1);
+        ensure_table(h, (size_t)h->hc.m_rows + window_rows() + 1);
 
         c.cursor = range_a;
         c.n_points = N;
@@ -1911,11 +1936,16 @@ struct OnlineRun {
             const int list_cap = (int)std::min<size_t>(h->tab.cap, (size_t)INT_MAX / 2);
             h->seq_lists.ensure(2 * (size_t)list_cap);
             h->seq_img.ensure(4 * (size_t)list_cap * (size_t)h->d);
-#define CC_SEQG(F, P) hipLaunchKernelGGL((k_seq_g<F, P>), dim3(1), dim3(CC_SEQG_THREADS), 0, sA, h->ctl.p, h->X.p, tab, h->lab_uid.p, h->lab_path.p, chunk, h->seq_lists.p, list_cap, h->seq_img.p)
-            if (f && p2) CC_SEQG(true, true);
-            else if (f) CC_SEQG(true, false);
-            else if (p2) CC_SEQG(false, true);
-            else CC_SEQG(false, false);
+#define CC_SEQG(F, P, W) hipLaunchKernelGGL((k_seq_g<F, P, W>), dim3(1), dim3(CC_SEQG_THREADS), 0, sA, h->ctl.p, h->X.p, tab, h->lab_uid.p, h->lab_path.p, chunk, h->seq_lists.p, list_cap, h->seq_img.p)
+            if (h->d > CC_SEQG_NARROW_DIM) {  // (the wide form: a point's dimensions in blocks of 64)
+                if (f && p2) CC_SEQG(true, true, true);
+                else if (f) CC_SEQG(true, false, true);
+                else if (p2) CC_SEQG(false, true, true);
+                else CC_SEQG(false, false, true);
+            } else if (f && p2) CC_SEQG(true, true, false);
+            else if (f) CC_SEQG(true, false, false);
+            else if (p2) CC_SEQG(false, true, false);
+            else CC_SEQG(false, false, false);
 #undef CC_SEQG
         } else {
             const bool f = h->hc.filter != 0, p2 = h->hc.pow2 != 0;
@@ -2409,7 +2439,7 @@ struct OnlineRun {
     {
         prepare();
         while (done < N) {
-            ensure_table(h, (size_t)m_known + std::max<size_t>((size_t)win * batch_max, seq_on ? 8192 : 0) + 1);
+            ensure_table(h, (size_t)m_known + std::max<size_t>(window_rows(), seq_on ? 8192 : 0) + 1);
             const Table tab = h->tab.view();
             if (seq_on) {
                 sequential_stint(tab);
@@ -2761,7 +2791,9 @@ int cc_offline(cc_handle* h, int32_t* n_clusters, int8_t* out_core, int32_t* out
                 else if (d <= 24) CC_EPS(24);
                 else if (d <= 40) CC_EPS(40);
                 else if (d <= 64) CC_EPS(64);
-                else CC_EPS(128);
+                else if (d <= 128) CC_EPS(128);
+                else hipLaunchKernelGGL(k_eps_neighbours_blk, grid, block, 0, h->stream, pv.cen, mp, d, p.ups_eps, h->adj.p, words,
+                                        p_lo, p_hi, pch);
 #undef CC_EPS
             }
             hipLaunchKernelGGL(k_subspace_pref, dim3((unsigned)(((size_t)my_rows * d + 255) / 256)), dim3(256), 0, h->stream,
@@ -2988,7 +3020,11 @@ int cc_assoc_argmin(cc_handle* h, const double* cur_cen, const double* cur_pref,
             else if (d <= 24) CC_ASSOC(24);
             else if (d <= 40) CC_ASSOC(40);
             else if (d <= 64) CC_ASSOC(64);
-            else CC_ASSOC(128);
+            else if (d <= 128) CC_ASSOC(128);
+            else if (unit) hipLaunchKernelGGL((k_assoc_tiled_blk<true>), grid, block, 0, h->stream, h->a_cur_cen.p, h->a_cur_pref.p,
+                                              h->a_prev_cen.p, mc, mp, d, c_lo, c_hi, h->a_pdist.p, h->a_pidx.p);
+            else hipLaunchKernelGGL((k_assoc_tiled_blk<false>), grid, block, 0, h->stream, h->a_cur_cen.p, h->a_cur_pref.p,
+                                    h->a_prev_cen.p, mc, mp, d, c_lo, c_hi, h->a_pdist.p, h->a_pidx.p);
 #undef CC_ASSOC
             hipLaunchKernelGGL(k_assoc_merge, dim3((c_hi - c_lo + 255) / 256), dim3(256), 0, h->stream, h->a_pdist.p,
                                h->a_pidx.p, S, mc, c_lo, c_hi, h->a_idx.p, h->a_dist.p);

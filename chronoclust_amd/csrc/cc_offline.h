@@ -176,6 +176,62 @@ __global__ __launch_bounds__(256) void k_eps_neighbours(const double* __restrict
     }
 }
 
+// K6 beyond 128 dimensions (k_eps_neighbours holds q's whole centroid in registers, which stops there): the same with the
+// dimensions in blocks of CC_EPS_BD.  Per tile of CC_EPS_TP p rows every lane carries one sum per p row across the blocks;
+// a block of q's centroid is loaded into registers and the same block of the p tile is staged in LDS, then the next block.
+// Each pair's sum stays one left-to-right sum over all d (padded dimensions: 0 - 0); the square root, the comparison and
+// the ballot follow the last block.
+#define CC_EPS_BD 32
+
+__global__ __launch_bounds__(256) void k_eps_neighbours_blk(const double* __restrict__ cen, int mp, int d, double eps,
+                                                            unsigned long long* __restrict__ adj, int words, int p_base,
+                                                            int p_end, int pch)
+{
+    __shared__ __attribute__((aligned(16))) double s_p[CC_EPS_TP * CC_EPS_BD];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int qword = blockIdx.x * 4 + wv;
+    const int q = qword * 64 + lane;
+    const bool qvalid = qword < words && q < mp;
+    const int p0 = p_base + blockIdx.y * pch;
+    const int p1 = min(p_end, p0 + pch);
+    for (int pt = p0; pt < p1; pt += CC_EPS_TP) {
+        const int tp = min(CC_EPS_TP, p1 - pt);
+        double acc[CC_EPS_TP];
+#pragma unroll
+        for (int m = 0; m < CC_EPS_TP; ++m) acc[m] = 0.0;
+        for (int i0 = 0; i0 < d; i0 += CC_EPS_BD) {
+            double cq[CC_EPS_BD];
+#pragma unroll
+            for (int i = 0; i < CC_EPS_BD; ++i) cq[i] = (qvalid && i0 + i < d) ? cen[(size_t)q * d + i0 + i] : 0.0;
+            __syncthreads();  // (the previous block has been consumed)
+            for (int e = threadIdx.x; e < CC_EPS_TP * CC_EPS_BD; e += 256) {
+                const int m = e / CC_EPS_BD, i = e - m * CC_EPS_BD;
+                s_p[e] = (m < tp && i0 + i < d) ? cen[(size_t)(pt + m) * d + i0 + i] : 0.0;
+            }
+            __syncthreads();
+            if (qword >= words) continue;  // (a wave without a word of its own still helps staging)
+#pragma unroll
+            for (int m = 0; m < CC_EPS_TP; ++m) {
+#pragma unroll
+                for (int i = 0; i < CC_EPS_BD; ++i) {
+                    double t = cq[i] - s_p[m * CC_EPS_BD + i];  // predeconmc_functions.py:4-17
+                    t = t * t;
+                    acc[m] = acc[m] + t;
+                }
+            }
+        }
+        if (qword >= words) continue;
+#pragma unroll
+        for (int m = 0; m < CC_EPS_TP; ++m) {
+            if (m < tp) {
+                const bool in = qvalid && sqrt(acc[m]) <= eps;
+                const unsigned long long mask = __builtin_amdgcn_ballot_w64(in);
+                if (lane == 0) adj[(size_t)(pt + m) * words + qword] = mask;
+            }
+        }
+    }
+}
+
 // K7: predecon.py:190-217 + predeconmc_functions.py:19-42.  One thread per (p, dim): mean squared deviation of
 // the neighbours' centroids, summed in dict (= list) order.  Note `<= delta`, not delta^2 (predecon.py:213).
 __global__ void k_subspace_pref(const double* __restrict__ cen, const unsigned long long* __restrict__ adj,
@@ -379,6 +435,69 @@ __global__ __launch_bounds__(256) void k_assoc_tiled(const double* __restrict__ 
             }
             if (bidx < 0 || acc < best) {  // ascending q: strict < keeps the first minimum
                 best = acc;
+                bidx = qt + m;
+            }
+        }
+    }
+    if (valid) {
+        part_dist[(size_t)blockIdx.y * mc + c] = best;
+        part_idx[(size_t)blockIdx.y * mc + c] = bidx;
+    }
+}
+
+// K9 beyond 128 dimensions: the same with the dimensions in blocks of CC_ASSOC_BD (k_assoc_tiled holds a current pcore's
+// centroid and operands in registers, which stops there).  Per tile of CC_ASSOC_TQ previous pcores every lane carries one
+// sum per previous pcore across the blocks - a block of its centroid and operands in registers, the same block of the
+// previous centroids staged in LDS -, and the running minimum takes a pair only once its sum is complete, in ascending q.
+#define CC_ASSOC_BD 16
+
+template <bool UNIT>
+__global__ __launch_bounds__(256) void k_assoc_tiled_blk(const double* __restrict__ cur_cen, const double* __restrict__ cur_op,
+                                                         const double* __restrict__ prev_cen, int mc, int mp, int d, int c_lo,
+                                                         int c_hi, double* __restrict__ part_dist, int* __restrict__ part_idx)
+{
+    __shared__ __attribute__((aligned(16))) double s_q[CC_ASSOC_TQ * CC_ASSOC_BD];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = c_lo + (blockIdx.x * 4 + wv) * 64 + lane;
+    const bool valid = c < c_hi;
+    const int S = gridDim.y;
+    const int per = (mp + S - 1) / S;
+    const int q0 = blockIdx.y * per, q1 = min(mp, q0 + per);
+    double best = __builtin_huge_val();
+    int bidx = -1;
+    for (int qt = q0; qt < q1; qt += CC_ASSOC_TQ) {
+        const int tq = min(CC_ASSOC_TQ, q1 - qt);
+        double acc[CC_ASSOC_TQ];
+#pragma unroll
+        for (int m = 0; m < CC_ASSOC_TQ; ++m) acc[m] = 0.0;
+        for (int i0 = 0; i0 < d; i0 += CC_ASSOC_BD) {
+            double cc[CC_ASSOC_BD], op[CC_ASSOC_BD];
+#pragma unroll
+            for (int i = 0; i < CC_ASSOC_BD; ++i) {
+                cc[i] = (valid && i0 + i < d) ? cur_cen[(size_t)c * d + i0 + i] : 0.0;
+                op[i] = (valid && i0 + i < d) ? cur_op[(size_t)c * d + i0 + i] : 1.0;
+            }
+            __syncthreads();  // (the previous block has been consumed)
+            for (int e = threadIdx.x; e < CC_ASSOC_TQ * CC_ASSOC_BD; e += 256) {
+                const int m = e / CC_ASSOC_BD, i = e - m * CC_ASSOC_BD;
+                s_q[e] = (m < tq && i0 + i < d) ? prev_cen[(size_t)(qt + m) * d + i0 + i] : 0.0;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int m = 0; m < CC_ASSOC_TQ; ++m) {
+#pragma unroll
+                for (int i = 0; i < CC_ASSOC_BD; ++i) {
+                    double t = s_q[m * CC_ASSOC_BD + i] - cc[i];  // padded dimensions: 0 - 0, operand 1: the terms add +0.0
+                    t = t * t;
+                    t = UNIT ? t * op[i] : ((op[i] != 1.0) ? t / op[i] : t);
+                    acc[m] = acc[m] + t;
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < CC_ASSOC_TQ; ++m) {
+            if (m < tq && (bidx < 0 || acc[m] < best)) {  // ascending q: strict < keeps the first minimum
+                best = acc[m];
                 bidx = qt + m;
             }
         }

@@ -44,21 +44,25 @@ __global__ __launch_bounds__(256) void k_check_finite(const double* __restrict__
 // chronoclust_amd/scaling/scaler.py): HBM-bound elementwise passes and one column reduction.
 // ---------------------------------------------------------------------------------
 
-// per-column minimum / maximum ignoring NaN (np.nanmin / np.nanmax): one workgroup per (column, row chunk),
-// coalescing is across the columns of a row (consecutive threads read consecutive doubles), partials in part[2][chunks][d]
+// per-column minimum / maximum ignoring NaN (np.nanmin / np.nanmax): one workgroup per row chunk, coalescing is across the
+// columns of a row (consecutive threads read consecutive doubles), partials in part[2][chunks][d].  BLOCKED (d > 256): one
+// workgroup per (row chunk, block of 256 columns: blockIdx.y), each block reduced like a table of at most 256 columns.
+template <bool BLOCKED>
 __global__ __launch_bounds__(256) void k_col_minmax(const double* __restrict__ x, long long n, int d,
                                                     double* __restrict__ part, int chunks)
 {
-    // thread t handles column t % d of rows t / d, t / d + rows_per_pass, ...
-    const int rows_per_pass = 256 / d > 0 ? 256 / d : 1;
-    const int col = (d <= 256) ? (int)(threadIdx.x % d) : 0;
-    const int rsub = (int)(threadIdx.x / d);
+    // this workgroup's columns c0 .. c0 + db - 1: thread t handles column c0 + t % db of rows t / db, t / db + rows_per_pass, ...
+    const int c0 = BLOCKED ? (int)blockIdx.y * 256 : 0;
+    const int db = BLOCKED ? ((d - c0) < 256 ? d - c0 : 256) : d;
+    const int rows_per_pass = 256 / db > 0 ? 256 / db : 1;
+    const int col = (db <= 256) ? (int)(threadIdx.x % db) : 0;
+    const int rsub = (int)(threadIdx.x / db);
     const long long per = (n + chunks - 1) / chunks;
     const long long r0 = (long long)blockIdx.x * per, r1 = (r0 + per < n) ? r0 + per : n;
     double mn = CC_INF, mx = -CC_INF;
-    if (rsub < rows_per_pass && d <= 256)
+    if (rsub < rows_per_pass && db <= 256)
         for (long long r = r0 + rsub; r < r1; r += rows_per_pass) {
-            const double v = x[r * d + col];
+            const double v = x[r * d + c0 + col];
             mn = __builtin_fmin(mn, v);  // fmin / fmax return the non-NaN operand
             mx = __builtin_fmax(mx, v);
         }
@@ -66,13 +70,13 @@ __global__ __launch_bounds__(256) void k_col_minmax(const double* __restrict__ x
     smn[threadIdx.x] = mn;
     smx[threadIdx.x] = mx;
     __syncthreads();
-    if ((int)threadIdx.x < d && d <= 256) {
+    if ((int)threadIdx.x < db && db <= 256) {
         for (int q = 1; q < rows_per_pass; ++q) {
-            mn = __builtin_fmin(mn, smn[q * d + threadIdx.x]);
-            mx = __builtin_fmax(mx, smx[q * d + threadIdx.x]);
+            mn = __builtin_fmin(mn, smn[q * db + threadIdx.x]);
+            mx = __builtin_fmax(mx, smx[q * db + threadIdx.x]);
         }
-        part[(size_t)blockIdx.x * d + threadIdx.x] = mn;
-        part[(size_t)(chunks + blockIdx.x) * d + threadIdx.x] = mx;
+        part[(size_t)blockIdx.x * d + c0 + threadIdx.x] = mn;
+        part[(size_t)(chunks + blockIdx.x) * d + c0 + threadIdx.x] = mx;
     }
 }
 

@@ -19,10 +19,15 @@
 // before everybody's loads of the next point.  Same arithmetic, same order of operations as k_seq.
 // ---------------------------------------------------------------------------------
 
+// WIDE (d > CC_SEQG_NARROW_DIM, up to CC_MAX_DIM): the first wave walks a point's dimensions in blocks of 64 (lane =
+// dimension within the block) and reads the point from LDS, where the narrow form holds two dimensions per lane in
+// registers; a chunk stages CC_SEQG_WIDE_DOUBLES / d points, one at least.  Everything else is the same code.
 #define CC_SEQG_THREADS 1024
 #define CC_SEQG_CHUNK_DOUBLES 512  // points staged per chunk: 512 / d of them (four at d = 128), at most 64
+#define CC_SEQG_NARROW_DIM 128     // the narrow form: dimensions lane and lane + 64 of the first wave
+#define CC_SEQG_WIDE_DOUBLES CC_MAX_DIM  // the wide form's chunk: 1 024 / d points (one beyond 512 dimensions)
 
-template <bool FILTER, bool POW2>
+template <bool FILTER, bool POW2, bool WIDE = false>
 __global__ __launch_bounds__(CC_SEQG_THREADS) void k_seq_g(Ctl* __restrict__ ctl, const double* __restrict__ X, Table tab,
                                                             long long* __restrict__ lab_uid, int8_t* __restrict__ lab_path,
                                                             int n_max, int* __restrict__ lists, int list_cap,
@@ -45,7 +50,8 @@ __global__ __launch_bounds__(CC_SEQG_THREADS) void k_seq_g(Ctl* __restrict__ ctl
     // x / pref through the operand (mc_functions.py:39)
     auto scaled = [&](double x, double op) { return pow2 ? x * op : (op == 1.0 ? x : x / op); };
 
-    __shared__ __attribute__((aligned(16))) double s_pts[CC_SEQG_CHUNK_DOUBLES];
+    constexpr int CHUNK_DOUBLES = WIDE ? CC_SEQG_WIDE_DOUBLES : CC_SEQG_CHUNK_DOUBLES;
+    __shared__ __attribute__((aligned(16))) double s_pts[CHUNK_DOUBLES];
     __shared__ double s_cd[NW];          // per wave: best distance, key, row, list position
     __shared__ int s_ck[NW], s_cr[NW], s_cq[NW];
     __shared__ int s_np, s_no;
@@ -86,7 +92,7 @@ __global__ __launch_bounds__(CC_SEQG_THREADS) void k_seq_g(Ctl* __restrict__ ctl
 #define CC_TQ(i) do { } while (0)
 #endif
 
-    const int C = (CC_SEQG_CHUNK_DOUBLES / d) < 64 ? (CC_SEQG_CHUNK_DOUBLES / d) : 64;
+    const int C = (CHUNK_DOUBLES / d) < 64 ? (CHUNK_DOUBLES / d) : 64;
     int done = 0;
     bool full = false;
     for (int c0 = 0; c0 < n && !full; c0 += C) {
@@ -98,7 +104,7 @@ __global__ __launch_bounds__(CC_SEQG_THREADS) void k_seq_g(Ctl* __restrict__ ctl
         int cdone = 0;
         for (int jj = 0; jj < cnt; ++jj) {
             const double* sp = s_pts + jj * d;
-            // (first wave) this lane's dimensions of the point: lane and lane + 64 (d <= 128 = CC_MAX_DIM)
+            // (first wave, narrow form) this lane's dimensions of the point: lane and lane + 64 (d <= CC_SEQG_NARROW_DIM)
             const double myp[2] = {(tid < d) ? sp[tid] : 0.0, (tid < 64 && tid + 64 < d) ? sp[tid + 64] : 0.0};
             int target = -1, path = 2;
             bool promoted = false;
@@ -255,7 +261,70 @@ __global__ __launch_bounds__(CC_SEQG_THREADS) void k_seq_g(Ctl* __restrict__ ctl
                     continue;
                 }
                 // tentative add (microcluster.py:213-233) with lane = dimension, then the radius test (:334-337 / :378-381)
-                if (wave == 0) {
+                if (WIDE && wave == 0) {
+                    // the same per block of 64 dimensions: the terms of a block join the radius sum in order before the
+                    // next block's (one left-to-right sum over all d); the commit takes the sums again from the row, which
+                    // nothing has written yet
+                    const double w1 = tab.w[R] + 1.0;
+                    double r2 = 0.0;
+#pragma nounroll
+                    for (int i0 = 0; i0 < d; i0 += 64) {
+                        const int i = i0 + lane;
+                        double term = 0.0;
+                        if (i < d) {
+                            const double x = sp[i];
+                            const double c1 = tab.cf1[(size_t)R * d + i] + x;
+                            const double c2 = tab.cf2[(size_t)R * d + i] + x * x;
+                            const double qa = c2 / w1;
+                            const double qb = c1 / w1;
+                            const double var = qa - qb * qb;
+                            const double pr = (var <= par.delta_sq) ? par.k : 1.0;
+                            term = scaled(var, op_of(pr));  // mc_functions.py:52: var / pref'
+                        }
+                        const int nb = (d - i0) < 64 ? d - i0 : 64;
+#pragma nounroll
+                        for (int l = 0; l < nb; ++l) r2 = r2 + cc_readlane_f64(term, l);  // mc_functions.py:54, left to right
+                    }
+                    int verdict = 0;
+                    if (r2 <= par.eps_sq) {
+                        verdict = 1;
+                        int gt1 = 0;
+#pragma nounroll
+                        for (int i0 = 0; i0 < d; i0 += 64) {
+                            const int i = i0 + lane;
+                            double pr = 1.0;
+                            if (i < d) {
+                                const double x = sp[i];
+                                const size_t o = (size_t)R * d + i;
+                                const double c1 = tab.cf1[o] + x;
+                                const double c2 = tab.cf2[o] + x * x;
+                                const double qa = c2 / w1;
+                                const double qb = c1 / w1;
+                                const double var = qa - qb * qb;
+                                pr = (var <= par.delta_sq) ? par.k : 1.0;
+                                tab.cf1[o] = c1; tab.cf2[o] = c2; tab.cen[o] = qb; tab.pref[o] = pr; tab.scl[o] = op_of(pr);
+                                const size_t io = (size_t)i * list_cap + R;
+                                icen[io] = qb; iscl[io] = op_of(pr);
+                                if (FILTER) { ic1[io] = c1; ic2[io] = c2; }
+                            }
+                            gt1 += __builtin_popcountll(__builtin_amdgcn_ballot_w64(i < d && pr > 1.0));
+                        }
+                        if (lane == 0) tab.w[R] = w1;
+                        if (stage == 1) {
+                            // hddstream.py:416-430
+                            if (w1 >= par.beta_mu && gt1 <= par.pi) {
+                                verdict = 3;
+                                // out of the outlier list (the last entry takes its place), onto the pcore list
+                                if (lane == 0) {
+                                    tab.kind[R] = CC_KIND_PCORE; tab.key[R] = n_pkeys; tab.id[R] = pcore_last_id;
+                                    olist[Q] = olist[n_o - 1];
+                                    plist[n_p] = R;
+                                }
+                            }
+                        }
+                    }
+                    if (lane == 0) s_verdict = verdict;
+                } else if (wave == 0) {
                     const double w1 = tab.w[R] + 1.0;
                     double c1[2] = {0.0, 0.0}, c2[2] = {0.0, 0.0}, qb[2] = {0.0, 0.0}, pr[2] = {1.0, 1.0}, term[2] = {0.0, 0.0};
 #pragma unroll
@@ -331,6 +400,21 @@ __global__ __launch_bounds__(CC_SEQG_THREADS) void k_seq_g(Ctl* __restrict__ ctl
                 if (M >= (int)tab.cap || n_o >= list_cap) { full = true; break; }  // (the host makes room and comes back)
                 const int R = M;
                 if (wave == 0) {
+                    if (WIDE) {
+#pragma nounroll
+                        for (int i = lane; i < d; i += 64) {
+                            const double x = sp[i];
+                            const double c1 = 0.0 + x, c2 = 0.0 + x * x;
+                            const double qa = c2 / 1.0, qb = c1 / 1.0;
+                            const double var = qa - qb * qb;
+                            const double pr = (var <= par.delta_sq) ? par.k : 1.0;
+                            const size_t o = (size_t)R * d + i;
+                            tab.cf1[o] = c1; tab.cf2[o] = c2; tab.cen[o] = qb; tab.pref[o] = pr; tab.scl[o] = op_of(pr);
+                            const size_t io = (size_t)i * list_cap + R;
+                            icen[io] = qb; iscl[io] = op_of(pr);
+                            if (FILTER) { ic1[io] = c1; ic2[io] = c2; }
+                        }
+                    } else
 #pragma unroll
                     for (int hh = 0; hh < 2; ++hh) {
                         const int i = lane + 64 * hh;

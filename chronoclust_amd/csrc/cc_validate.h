@@ -1360,6 +1360,7 @@ __global__ __launch_bounds__(256) void k_chain(Ctl* __restrict__ ctl, const doub
 // ---------------------------------------------------------------------------------
 
 #define CC_LONG_XY_DOUBLES 6144  // staged CF1 / CF2 prefixes of a batch: 2 * K * d doubles (48 KB)
+#define CC_LONG_PAD_DIM 128      // the staging area's pad: sized for 128 dimensions (the windowed path stops at CC_WINDOW_MAX_DIM)
 #define CC_LONG_QUEUE 2048       // pending chain members (ring buffer); four times as many in the SPLIT workgroups
 #define CC_LONG_THREADS 1024      // threads of a k_chain_long workgroup
 
@@ -1444,10 +1445,10 @@ __global__ __launch_bounds__(SPLIT ? CC_LONG_THREADS : 256) void k_chain_long(Ct
     // steps per batch: the CF1 / CF2 prefixes of a batch have to fit the staging area
     const int K = min(256, (CC_LONG_XY_DOUBLES / (2 * d)) & ~7);  // (256 at d <= 12, 216 at 14, 152 at 20, 72 at 40, 48 at 64)
 
-    __shared__ __attribute__((aligned(16))) double s_xy[CC_LONG_XY_DOUBLES + 2 * CC_MAX_DIM];  // (+ one odd-length pad per dimension)
+    __shared__ __attribute__((aligned(16))) double s_xy[CC_LONG_XY_DOUBLES + 2 * CC_LONG_PAD_DIM];  // (+ one odd-length pad per dimension)
     __shared__ double s_w[256], s_dq[256];
     // (PREP: a second staging area - the running sums of one batch run beside the staging of the next, see the loop)
-    __shared__ __attribute__((aligned(16))) double s_xy2[PREP && SPLIT ? CC_LONG_XY_DOUBLES + 2 * CC_MAX_DIM : 1];
+    __shared__ __attribute__((aligned(16))) double s_xy2[PREP && SPLIT ? CC_LONG_XY_DOUBLES + 2 * CC_LONG_PAD_DIM : 1];
     __shared__ double s_w2[PREP && SPLIT ? 256 : 1];
     __shared__ unsigned long long s_mask[256];  // bit i: dimension i is a preferred one after the step (var <= delta^2)
     __shared__ int s_flag[256];                 // bit 0: radius test passed, bit 1: promotion condition holds
