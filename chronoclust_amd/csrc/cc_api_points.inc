@@ -1,0 +1,220 @@
+// cc_api_points.inc — the C-ABI entry points that bring points to the device and back: upload (plain, scaled, adopted from a
+// prefetch), the column minima / maxima of the scaler, the prefetch worker, download.  (included by cc_api.hip, the one
+// translation unit, behind cc_handle.h)
+
+extern "C" {
+
+static int upload_points(cc_handle* h, const double* x, int64_t n, int32_t d, const double* scale, const double* mn);
+
+int cc_points_upload(cc_handle* h, const double* x, int64_t n, int32_t d)
+{
+    if (!h || (!x && n > 0) || n < 0) return CC_ERR_BAD_ARG;
+    return guarded(h, [&]() { return upload_points(h, x, n, d, nullptr, nullptr); });
+}
+
+// MinMax scaling on the device (scaling/scaler.py:27-47).  cc_col_minmax: per-column min / max of a host buffer,
+// NaN ignored (what MinMaxScaler.partial_fit takes from one file); cc_points_upload_scaled: cc_points_upload of
+// x * scale + min_; cc_points_download_unscaled: (resident points - min_) / scale back to the host.
+int cc_col_minmax(cc_handle* h, const double* x, int64_t n, int32_t d, double* out_min, double* out_max)
+{
+    if (!h || !x || n <= 0 || !out_min || !out_max) return CC_ERR_BAD_ARG;
+    if (d <= 0 || d > CC_MAX_DIM) return fail(h, CC_ERR_BAD_ARG, "d must be in 1.." + std::to_string(CC_MAX_DIM));
+    return guarded(h, [&]() {
+        h->scr.ensure((size_t)n * d);
+        const int chunks = (int)std::min<long long>(1024, (n + 255) / 256);
+        h->scr2.ensure((size_t)2 * chunks * d);
+        HIPCHK(hipMemcpyAsync(h->scr.p, x, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
+        if (d <= 256)
+            hipLaunchKernelGGL(k_col_minmax<false>, dim3(chunks), dim3(256), 0, h->stream, h->scr.p, (long long)n, (int)d,
+                               h->scr2.p, chunks);
+        else
+            hipLaunchKernelGGL(k_col_minmax<true>, dim3(chunks, (d + 255) / 256), dim3(256), 0, h->stream, h->scr.p,
+                               (long long)n, (int)d, h->scr2.p, chunks);
+        std::vector<double> part((size_t)2 * chunks * d);
+        HIPCHK(hipMemcpyAsync(part.data(), h->scr2.p, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        sync_stream(h, h->stream);
+        for (int c = 0; c < d; ++c) {
+            double mn = std::numeric_limits<double>::infinity(), mx = -mn;
+            for (int b = 0; b < chunks; ++b) {
+                mn = std::fmin(mn, part[(size_t)b * d + c]);
+                mx = std::fmax(mx, part[(size_t)(chunks + b) * d + c]);
+            }
+            out_min[c] = mn;
+            out_max[c] = mx;
+        }
+        return (int)CC_OK;
+    });
+}
+
+// waits for a running prefetch; returns true if it finished without an error
+static bool prefetch_join(cc_handle* h)
+{
+    if (h->pf.worker.joinable()) h->pf.worker.join();
+    return h->pf.active && h->pf.rc == 0;
+}
+
+static void prefetch_discard(cc_handle* h)
+{
+    (void)prefetch_join(h);
+    h->pf.active = false;
+}
+
+// the largest |value| k_check_finite saw (words 2..3 of its flag buffer)
+static double absmax_of(const int* flag_words)
+{
+    double m;
+    memcpy(&m, flag_words + 2, 8);
+    return m;
+}
+
+static int upload_points(cc_handle* h, const double* x, int64_t n, int32_t d, const double* scale, const double* mn)
+{
+    int rc = set_dim(h, d);
+    if (rc != CC_OK) return rc;
+    if (h->pf.active) {
+        // the points may already be on their way (cc_points_prefetch): adopt them if it is this very upload
+        cc_handle::Prefetch& pf = h->pf;
+        bool same = pf.x == x && pf.n == n && pf.d == d && pf.scaled == (scale != nullptr);
+        for (int i = 0; same && scale && i < d; ++i) same = pf.scale[i] == scale[i] && pf.mn[i] == mn[i];
+        const bool ok = prefetch_join(h);
+        pf.active = false;
+        if (same && ok) {
+            h->X.swap(pf.X);
+            h->Xt.swap(pf.Xt);
+            h->lab_uid.ensure((size_t)n);
+            h->lab_path.ensure((size_t)n);
+            h->n_points = n;
+            if (pf.bad_host[0]) {
+                h->n_points = 0;
+                return fail(h, CC_ERR_NONFINITE, "input points contain NaN or Inf");
+            }
+            h->x_absmax = absmax_of(pf.bad_host);
+            return (int)CC_OK;
+        }
+    }
+    h->X.ensure((size_t)n * d);
+    h->Xt.ensure((size_t)n * d);
+    h->lab_uid.ensure((size_t)n);
+    h->lab_path.ensure((size_t)n);
+    h->n_points = n;
+    if (n == 0) return (int)CC_OK;
+    HIPCHK(hipMemcpyAsync(h->X.p, x, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->badflag.p, 0, 16, h->stream));
+    const long long tot = (long long)n * d;
+    if (scale) {
+        h->scr2.ensure((size_t)2 * d);
+        HIPCHK(hipMemcpyAsync(h->scr2.p, scale, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->scr2.p + d, mn, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->X.p, tot, (int)d,
+                           h->scr2.p, h->scr2.p + d);
+    }
+    int blocks = (int)std::min<long long>((tot + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_check_finite, dim3(blocks), dim3(256), 0, h->stream, h->X.p, tot, h->badflag.p);
+    hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->X.p,
+                       h->Xt.p, (long long)n, (int)d);
+    int bad[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(bad, h->badflag.p, 16, hipMemcpyDeviceToHost, h->stream));
+    sync_stream(h, h->stream);
+    if (bad[0]) {
+        h->n_points = 0;
+        return fail(h, CC_ERR_NONFINITE, "input points contain NaN or Inf");
+    }
+    h->x_absmax = absmax_of(bad);
+    return (int)CC_OK;
+}
+
+int cc_points_prefetch(cc_handle* h, const double* x, int64_t n, int32_t d, const double* scale, const double* min_)
+{
+    if (!h || !x || n <= 0 || ((scale == nullptr) != (min_ == nullptr))) return CC_ERR_BAD_ARG;
+    if (d <= 0 || d > CC_MAX_DIM) return fail(h, CC_ERR_BAD_ARG, "d must be in 1.." + std::to_string(CC_MAX_DIM));
+    return guarded(h, [&]() {
+        prefetch_discard(h);
+        cc_handle::Prefetch& pf = h->pf;
+        pf.x = x; pf.n = n; pf.d = d; pf.scaled = scale != nullptr;
+        pf.scale.assign(scale ? scale : x, scale ? scale + d : x);
+        pf.mn.assign(min_ ? min_ : x, min_ ? min_ + d : x);
+        pf.rc = 0; pf.what = ""; pf.bad_host[0] = pf.bad_host[1] = pf.bad_host[2] = pf.bad_host[3] = 0;
+        if (!pf.stream) HIPCHK(hipStreamCreateWithFlags(&pf.stream, hipStreamNonBlocking));
+        const size_t chunk = (size_t)16 << 20;
+        if (pf.pin_bytes < chunk) {
+            for (int q = 0; q < 2; ++q) {
+                if (pf.pin[q]) (void)hipHostFree(pf.pin[q]);
+                pf.pin[q] = nullptr;
+                HIPCHK(hipHostMalloc(&pf.pin[q], chunk, hipHostMallocDefault));
+            }
+            pf.pin_bytes = chunk;
+        }
+        pf.X.ensure((size_t)n * d); pf.Xt.ensure((size_t)n * d); pf.sm.ensure((size_t)2 * d); pf.bad.ensure(4);
+        pf.active = true;
+        const int device = h->device;
+        pf.worker = std::thread([&pf, device, chunk]() {
+            auto chk = [&](hipError_t e, const char* what) {
+                if (e != hipSuccess && pf.rc == 0) { pf.rc = (int)e; pf.what = what; }
+                return e == hipSuccess;
+            };
+            if (!chk(hipSetDevice(device), "hipSetDevice")) return;
+            const size_t bytes = (size_t)pf.n * pf.d * 8;
+            hipEvent_t ev[2] = {nullptr, nullptr};
+            for (int q = 0; q < 2; ++q)
+                if (!chk(hipEventCreateWithFlags(&ev[q], hipEventDisableTiming), "hipEventCreate")) return;
+            int k = 0;
+            for (size_t off = 0; off < bytes && pf.rc == 0; off += chunk, k ^= 1) {
+                const size_t len = std::min(chunk, bytes - off);
+                if (off >= 2 * chunk) chk(hipEventSynchronize(ev[k]), "hipEventSynchronize");  // the staging buffer is free again
+                memcpy(pf.pin[k], (const char*)pf.x + off, len);
+                chk(hipMemcpyAsync((char*)pf.X.p + off, pf.pin[k], len, hipMemcpyHostToDevice, pf.stream), "hipMemcpyAsync");
+                chk(hipEventRecord(ev[k], pf.stream), "hipEventRecord");
+            }
+            const long long tot = pf.n * (long long)pf.d;
+            if (pf.rc == 0) {
+                chk(hipMemsetAsync(pf.bad.p, 0, 16, pf.stream), "hipMemsetAsync");
+                if (pf.scaled) {
+                    chk(hipMemcpyAsync(pf.sm.p, pf.scale.data(), (size_t)pf.d * 8, hipMemcpyHostToDevice, pf.stream), "hipMemcpyAsync");
+                    chk(hipMemcpyAsync(pf.sm.p + pf.d, pf.mn.data(), (size_t)pf.d * 8, hipMemcpyHostToDevice, pf.stream), "hipMemcpyAsync");
+                    hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, pf.stream, pf.X.p, tot,
+                                       pf.d, pf.sm.p, pf.sm.p + pf.d);
+                }
+                const int blocks = (int)std::min<long long>((tot + 255) / 256, 4096);
+                hipLaunchKernelGGL(k_check_finite, dim3(blocks), dim3(256), 0, pf.stream, pf.X.p, tot, pf.bad.p);
+                hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, pf.stream, pf.X.p, pf.Xt.p,
+                                   pf.n, pf.d);
+                chk(hipMemcpyAsync(pf.bad_host, pf.bad.p, 16, hipMemcpyDeviceToHost, pf.stream), "hipMemcpyAsync");
+                chk(hipGetLastError(), "kernel launch");
+            }
+            chk(hipStreamSynchronize(pf.stream), "hipStreamSynchronize");
+            for (int q = 0; q < 2; ++q) (void)hipEventDestroy(ev[q]);
+        });
+        return (int)CC_OK;
+    });
+}
+
+int cc_points_upload_scaled(cc_handle* h, const double* x, int64_t n, int32_t d, const double* scale, const double* min_)
+{
+    if (!h || (!x && n > 0) || n < 0 || !scale || !min_) return CC_ERR_BAD_ARG;
+    return guarded(h, [&]() { return upload_points(h, x, n, d, scale, min_); });
+}
+
+int cc_points_download(cc_handle* h, double* out, const double* scale, const double* min_)
+{
+    if (!h || !out || ((scale == nullptr) != (min_ == nullptr))) return CC_ERR_BAD_ARG;
+    return guarded(h, [&]() {
+        const long long tot = h->n_points * (long long)h->d;
+        if (tot == 0) return (int)CC_OK;
+        const int d = h->d;
+        if (!scale) {
+            HIPCHK(hipMemcpyAsync(out, h->X.p, (size_t)tot * 8, hipMemcpyDeviceToHost, h->stream));
+        } else {
+            h->scr.ensure((size_t)tot);
+            h->scr2.ensure((size_t)2 * d);
+            HIPCHK(hipMemcpyAsync(h->scr2.p, scale, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->scr2.p + d, min_, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(k_unscale_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->X.p, h->scr.p,
+                               tot, d, h->scr2.p, h->scr2.p + d);
+            HIPCHK(hipMemcpyAsync(out, h->scr.p, (size_t)tot * 8, hipMemcpyDeviceToHost, h->stream));
+        }
+        sync_stream(h, h->stream);
+        return (int)CC_OK;
+    });
+}
+
+}  // extern "C"

@@ -10,7 +10,8 @@
 // counters as read back); no clock, no pointer, no HIP.  cc_policy_replay (C-ABI) runs it over recorded observations on
 // a machine without a GPU (tests/test_window_policy.py).
 // The one wall-clock rule of the library - handing a stream of short, truncated windows to the sequential kernel when
-// that measures faster - stays in cc_api.hip, is switched off inside a group, and only consumes Decision::bad from here.
+// that measures faster - stays in cc_online_run.h (OnlineRun), is switched off inside a group, and only consumes
+// Decision::bad from here.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -30,7 +31,7 @@ inline bool policy_want_shard(const cc_policy_config& c, int m_rows, bool pruned
 }
 
 // Points per millisecond the sequential kernel that WOULD take over is assumed to manage before it has been measured in
-// this call (the takeover rule of cc_api.hip compares the windows' measured rate with it).  k_seq_r (rows in registers,
+// this call (the takeover rule of cc_online_run.h compares the windows' measured rate with it).  k_seq_r (rows in registers,
 // d <= 4) ~0.6 us per point, k_seq (table in LDS) ~1.3 us, whatever the data.  k_seq_g (table in HBM, from `seq_cap` rows
 // on) is one workgroup of 1 024 threads that walks rows / 1 024 rows per thread: 8-14 us per point measured at 150-450
 // rows (profiles/r05_tool_seq_g.txt) - 100 points per ms up to 1 024 rows, and in proportion to 1 024 / rows beyond: at

@@ -283,3 +283,19 @@ def test_mutable_microcluster_object_replays_the_reference_unit_tests():
     assert clone.cumulative_weight == 1 and clone.points == {}
     more = one.get_copy_with_new_point(np.array(cf1), 0.05, 4)
     assert more.cumulative_weight == 2 and one.cumulative_weight == 1 and list(more.preferred_dimension_vector) == [4] * len(cf1)
+
+
+def test_every_environment_knob_is_documented():
+    """Every CHRONOCLUST_HIP_* variable the library reads (csrc/, the package's Python files) is listed in INTEGRATION.md."""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pkg = os.path.join(root, "chronoclust_amd")
+    names = set()
+    for path in glob.glob(os.path.join(pkg, "csrc", "*")) + glob.glob(os.path.join(pkg, "*.py")):
+        with open(path, errors="replace") as f:
+            names |= set(re.findall(r"CHRONOCLUST_HIP_[A-Z0-9_]+", f.read()))
+    assert len(names) >= 30, sorted(names)  # (the scan found the sources)
+    with open(os.path.join(root, "INTEGRATION.md")) as f:
+        documented = set(re.findall(r"CHRONOCLUST_HIP_[A-Z0-9_]+", f.read()))
+    assert not names - documented, sorted(names - documented)
