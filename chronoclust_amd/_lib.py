@@ -79,6 +79,27 @@ class CcPolicyDecision(C.Structure):
                [(k, C.c_int64) for k in ("wins", "pts", "trunc", "unk", "tiles", "dtiles", "grew", "prune_rows", "prune_full")]
 
 
+class CcSeqEvent(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("chunk_event", "bad", "possible", "more", "seq_r_applies", "use_g", "allow_seq_g", "wide")] + \
+               [("got", C.c_int64), ("chunk", C.c_int64), ("rate", C.c_double), ("rate_guess", C.c_double)]
+
+
+class CcBatchInputs(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("window", "win_cfg", "S_cfg", "n_cus", "prune_now", "prune_wgs_per_cu", "plain_wgs_per_cu",
+                                         "decide_threads", "chain_threads", "commit_threads", "allow_claims", "allow_long",
+                                         "allow_heavy", "allow_prep", "m_rows", "n_heavy", "long_seen", "long_few")] + \
+               [("long_avg", C.c_int64), ("batch_windows", C.c_int32), ("pad", C.c_int32), ("points_left", C.c_int64)]
+
+
+LONG_NONE, LONG_ROWS_SPLIT, LONG_ROWS_SMALL, LONG_LIST_SPLIT, LONG_LIST_SMALL = range(5)
+
+
+class CcBatchGeometry(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("gw", "S", "sparse_cap", "dblocks", "cblocks", "rblocks", "scan_rows", "long_rows",
+                                         "long_listed", "heavy_on", "long_cap", "windows_now", "prep", "prep_form", "long_form",
+                                         "pad")]
+
+
 class CcRelaxedStats(C.Structure):
     _fields_ = [("super_steps", C.c_int64), ("minibatch_points", C.c_int64), ("deferred_points", C.c_int64),
                 ("reserved", C.c_int64 * 5)]
@@ -137,6 +158,8 @@ SYMBOLS = {
     "cc_comm_set_relaxed": (C.c_int, [C.c_void_p, C.c_int32]),
     "cc_get_relaxed_stats": (C.c_int, [C.c_void_p, C.POINTER(CcRelaxedStats)]),
     "cc_policy_seq_rate_guess": (C.c_double, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cc_seq_handover_replay": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(CcSeqEvent), C.c_int32, _i32p, _i64p]),
+    "cc_batch_plan": (C.c_int, [C.POINTER(CcBatchInputs), C.POINTER(CcBatchGeometry)]),
     "cc_shard_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p]),
     "cc_set_shard_thresholds": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
 }
@@ -169,13 +192,14 @@ def load():
     return _lib
 
 
-HOST_ONLY_SYMBOLS = ("cc_policy_replay", "cc_policy_seq_rate_guess", "cc_shard_rows", "cc_format_points_csv")
+HOST_ONLY_SYMBOLS = ("cc_policy_replay", "cc_policy_seq_rate_guess", "cc_seq_handover_replay", "cc_batch_plan", "cc_shard_rows",
+                     "cc_format_points_csv")
 
 
 def load_host_only(path):
     """Binds a library that holds only the entry points that are plain host code (csrc/cc_host_abi.inc built by itself: the
-    sanitizer builds of tests/host_san/) in the place of the HIP library, so that policy_replay, shard_rows and
-    format_points_csv of this module drive it.  Test infrastructure: nothing that needs a handle works afterwards."""
+    sanitizer builds of tests/host_san/) in the place of the HIP library, so that policy_replay, seq_handover_replay,
+    batch_plan, shard_rows and format_points_csv of this module drive it.  Test infrastructure: nothing that needs a handle works afterwards."""
     global _lib
     lib = C.CDLL(path)
     for name in HOST_ONLY_SYMBOLS:
@@ -285,6 +309,28 @@ def policy_replay(config, carry, start, observations):
         raise ValueError("cc_policy_replay: %s" % _ERRORS.get(rc, rc))
     keys = [k for k, _ in CcPolicyDecision._fields_ if k != "pad"]
     return [{k: getattr(d, k) for k in keys} for d in out], (car.adapt_win, car.clean_batches, car.since_shrink)
+
+
+def seq_handover_replay(mode, possible, sticky, events):
+    """cc_seq_handover_replay: the hand-over rule between the windows and the sequential kernel (cc::SeqHandover) over
+    events, no GPU and no clock.  events: dicts of cc_seq_event fields (chunk_event=1: a chunk of the sequential kernel, else a
+    batch of windows).  Returns (outcomes, stint lengths), one entry more than events: [0] is the start of the call."""
+    n = len(events)
+    ev = (CcSeqEvent * max(n, 1))(*[CcSeqEvent(**e) for e in events])
+    out, stint = (C.c_int32 * (n + 1))(), (C.c_int64 * (n + 1))()
+    rc = load().cc_seq_handover_replay(int(mode), int(possible), int(sticky), ev, n, out, stint)
+    if rc != 0:
+        raise ValueError("cc_seq_handover_replay: %s" % _ERRORS.get(rc, rc))
+    return list(out), list(stint)
+
+
+def batch_plan(**inputs):
+    """cc_batch_plan: the launch geometry of one batch of windows (cc::BatchPlan) from cc_batch_inputs fields, no GPU."""
+    out = CcBatchGeometry()
+    rc = load().cc_batch_plan(C.byref(CcBatchInputs(**inputs)), C.byref(out))
+    if rc != 0:
+        raise ValueError("cc_batch_plan(%r): %s" % (inputs, _ERRORS.get(rc, rc)))
+    return {k: getattr(out, k) for k, _ in CcBatchGeometry._fields_ if k != "pad"}
 
 
 def shard_rows(n, world, rank, unit=1):

@@ -26,6 +26,7 @@
 #include "cc_offline.h"
 #include "cc_online.h"
 #include "cc_policy.h"
+#include "cc_batch.h"
 
 #include "cc_handle.h"  // (behind the kernels' headers: its buffers are typed by their records)
 
@@ -337,21 +338,6 @@ void launch_scan(cc_handle* h, hipStream_t st, int win, Rows rows, const Cand* c
     }
     throw HipErr{hipErrorInvalidValue, "launch_scan before scan_plan() (OnlineRun::prepare)"};
 #undef CC_SCAN_DP
-}
-
-// Partials per point for a batch whose windows have `tiles` point tiles: at most S, not less than S / 2, chosen so that
-// the launch (tiles x S' workgroups) fills whole rounds of the resident workgroups - 1 024 workgroups on a machine that
-// holds 768 at once (d = 40) run as long as 1 536 would.
-int scan_partials_for(int tiles, int S, int resident)
-{
-    int best = S;
-    double best_eff = 0.0;
-    for (int s = S; s >= std::max(1, S / 2); --s) {
-        const double x = (double)tiles * s / (double)resident;
-        const double eff = x / std::ceil(x);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
-    }
-    return best;
 }
 
 }  // namespace

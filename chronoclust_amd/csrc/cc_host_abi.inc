@@ -1,7 +1,7 @@
 // cc_host_abi.inc - the C-ABI entry points that are plain host code (no handle, no HIP).  Included inside the extern "C"
 // block of cc_api.hip (the product) and of tests/host_san/host_abi.cpp (the same text under -fsanitize=address,undefined
 // and -fsanitize=thread, g++ only: sanitizers never touch the GPU build).  Needs chronoclust_hip.h, cc_host.h,
-// cc_policy.h, cc_csv.h.
+// cc_policy.h, cc_batch.h, cc_csv.h.
 
 int cc_shard_rows(int32_t n, int32_t world, int32_t rank, int32_t unit, int32_t* lo, int32_t* hi)
 {
@@ -59,5 +59,35 @@ double cc_policy_seq_rate_guess(int32_t d, int32_t m_rows, int32_t allow_seq_r, 
     if (d < 1 || d > CC_MAX_DIM || m_rows < 0) return -1.0;
     const int seq_cap = d > CC_WINDOW_MAX_DIM ? 0 : cc_seq_cap_rows(d);
     return cc::seq_rate_guess(d, m_rows, seq_cap, allow_seq_r != 0, allow_seq_g != 0);
+}
+
+int cc_seq_handover_replay(int32_t mode, int32_t possible, int32_t sticky, const cc_seq_event* ev, int32_t n, int32_t* outcome,
+                           int64_t* stint_len)
+{
+    if (mode < 0 || mode > 2 || n < 0 || (n > 0 && !ev) || !outcome || !stint_len) return CC_ERR_BAD_ARG;
+    cc::SeqHandover rule;
+    outcome[0] = rule.start(mode, possible != 0, sticky != 0) ? 1 : 0;
+    stint_len[0] = rule.stint_len();
+    for (int i = 0; i < n; ++i) {
+        const cc_seq_event& e = ev[i];
+        outcome[i + 1] = e.chunk_event
+                             ? (int32_t)rule.after_chunk(e.got, e.rate, e.chunk, e.use_g != 0, e.allow_seq_g != 0, e.possible != 0,
+                                                         e.more != 0, e.wide != 0)
+                             : (rule.after_batch(e.bad != 0, e.rate, e.possible != 0, e.more != 0, e.seq_r_applies != 0, e.rate_guess) ? 1 : 0);
+        stint_len[i + 1] = rule.stint_len();
+    }
+    return CC_OK;
+}
+
+int cc_batch_plan(const cc_batch_inputs* in, cc_batch_geometry* out)
+{
+    if (!in || !out) return CC_ERR_BAD_ARG;
+    for (int t : {in->decide_threads, in->chain_threads, in->commit_threads})
+        if (t != 64 && t != 128 && t != 256) return CC_ERR_BAD_ARG;
+    if (in->window < 1 || in->win_cfg < 0 || in->S_cfg < 1 || in->n_cus < 1 || in->prune_wgs_per_cu < 1 || in->plain_wgs_per_cu < 1 ||
+        in->m_rows < 0 || in->long_avg < 0 || in->points_left < 0)
+        return CC_ERR_BAD_ARG;
+    *out = cc::batch_plan(*in);
+    return CC_OK;
 }
 

@@ -1,6 +1,6 @@
 // cc_online_run.h — one call of the exact windowed online phase: OnlineRun (prepare, stints of the sequential kernel, batches
 // of windows enqueued and read back, finish), the trace of the window policy's decisions, and online_range(), its only
-// user.  Needs cc_handle.h and the scan dispatcher of cc_api.hip (launch_scan, scan_plan, scan_partials_for).
+// user.  Needs cc_handle.h, cc_policy.h, cc_batch.h and the scan dispatcher of cc_api.hip (launch_scan, scan_plan).
 // (included by cc_api.hip, the one translation unit)
 #pragma once
 
@@ -87,9 +87,87 @@ void launch_link_scan(cc_handle* h, hipStream_t st, int win)
 #undef CC_LINK_DP
 }
 
+static_assert(cc::kMaxWindow == CC_MAX_WINDOW && cc::kLongCap == CC_LONG_CAP, "cc_batch.h repeats two constants of cc_common.h");
+
+// The views the scans walk (Rows, cc_common.h), field by field on a zeroed struct: what a view does not have stays null
+Rows rows_of_table(const Table& t)
+{
+    Rows r{};
+    r.cen = t.cen; r.scl = t.scl; r.pref = t.pref; r.cf1 = t.cf1; r.cf2 = t.cf2; r.w = t.w; r.kind = t.kind; r.key = t.key;
+    return r;
+}
+Rows rows_of_versions(const Versions& v)
+{
+    Rows r{};
+    r.cen = v.cen; r.scl = v.scl; r.pref = v.pref; r.cf1 = v.cf1; r.cf2 = v.cf2; r.w = v.w; r.kind = v.kind; r.key = v.key;
+    r.next = v.next; r.tile_dsq = v.tile_dsq; r.dsq = v.dsq; r.tau = v.tau; r.skip = v.skip;
+    return r;
+}
+Rows rows_of_carry(const Carry& c, const Versions& v, const Table& t)
+{
+    Rows r{};
+    r.cen = c.cen; r.scl = c.scl; r.pref = c.pref; r.cf1 = c.cf1; r.cf2 = c.cf2; r.w = c.w; r.kind = c.kind; r.key = c.key;
+    r.tile_dsq = c.tile_dsq; r.dsq = c.dsq; r.tau = v.tau; r.skip = v.skip_car;
+    r.slot = c.slot; r.touch = t.touch; r.cap = t.cap;
+    return r;
+}
+// (lookahead scans read a scan copy of the table, see ScanCopy)
+Rows rows_of_scan_copy(const ScanCopy& s)
+{
+    Rows r{};
+    r.cen = s.cen; r.scl = s.scl; r.cf1 = s.cf1; r.cf2 = s.cf2; r.w = s.w; r.kind = s.kind; r.key = s.key;
+    return r;
+}
+// the sparse dirty scans: the same rows for the round's list of points instead of the window's tiles
+Rows sparse_rows(Rows r, const int* plist)
+{
+    r.skip = nullptr;
+    r.plist = plist;
+    return r;
+}
+
+// the counters of a call in the host mirror of the control block, before its first batch
+void reset_call_counters(Ctl& c)
+{
+    c.last_round = 0;
+    c.fc[0] = 0;
+    for (int i = 1; i < CC_MAX_ROUNDS + 2; ++i) c.fc[i] = CC_IDX_INF;
+    c.stat_windows = c.stat_rounds = c.stat_truncated = 0;
+    c.stat_lookahead = 0;
+    c.stat_tiles = c.stat_dirty_tiles = 0;
+    c.stat_unprovable = c.stat_unsafe = 0;
+    c.stat_long = 0;
+    for (int i = 0; i < CC_MAX_ROUNDS + 2; ++i) c.n_long[i] = 0;
+    c.stat_trunc_unknown = 0;
+    c.stat_table_rows = 0;
+    c.stat_seq_points = 0;
+    c.stat_seq_r_points = 0;
+#ifdef CC_LONG_TIMERS
+    for (int i = 0; i < 8; ++i) c.dbg_long[i] = 0;
+#endif
+#ifdef CC_ROUND_DEBUG
+    for (int i = 0; i < CC_MAX_ROUNDS + 2; ++i)
+        for (int q = 0; q < 6; ++q) c.dbg_round[i][q] = 0;
+#endif
+    c.n_heavy = c.n_heavy_new = 0;  // (rows are renumbered between calls: the marks of the last call are void)
+    c.stat_seq_clk = c.stat_seq_wall = 0;
+    c.stat_prune_rows = c.stat_prune_full = 0;
+    c.stat_missed = 0;
+    c.seed_at = -1;
+    for (int q = 0; q < 2; ++q) {
+        c.n_missed[q] = 0;
+        for (int K = 0; K < 2; ++K) { c.tg[q][K] = 0.0; c.tg_ok[q][K] = 0; }
+    }
+    c.cen_absmax = 0ull;            // (k_rebuild_scl takes the table's maximum into it)
+    c.stat_pair_rows = 0.0;
+    for (int i = 0; i < CC_MAX_ROUNDS + 2; ++i) c.round_hist[i] = 0;
+}
+
 // One call of the exact windowed online phase over the resident points [range_a, range_e): the state that lives across its
 // batches of windows, and what happens to it - prepare(), then per iteration either a stint of the sequential kernel or a
 // batch of windows enqueued (enqueue_batch) and read back (after_batch: the policy's decision for the next one) -, finish().
+// How a batch runs is decided in four places, none of them here: ScanPlan (cc_api.hip), cc::BatchPlan (cc_batch.h),
+// cc::WindowPolicy and cc::SeqHandover (cc_policy.h); this struct measures, carries the decisions out and launches.
 // online_range() below is its only user.
 struct OnlineRun {
     cc_handle* const h;
@@ -104,14 +182,13 @@ struct OnlineRun {
     bool grouped = false;
     size_t batch_max = 2;
     bool timing = false;
-    int seq_mode = 0, seq_cap = 0;
+    int seq_cap = 0;
     Versions ver{};
     Carry car{};
     hipStream_t sA = nullptr, sB = nullptr;
     static constexpr size_t ev_base = 4;
 
     // ---- the window policy and its current decision ----
-    cc_policy_config pcfg{};
     std::optional<cc::WindowPolicy> policy;
     std::optional<PolicyTrace> ptrace;
     cc_policy_decision dec{};
@@ -143,19 +220,18 @@ struct OnlineRun {
     double pair_rows_pruned = 0.0;                     // ... of those, by pruned chains
     long long sharded_windows = 0;
 
-    // ---- the sequential kernel's wall-clock rule (off inside a group) ----
-    bool seq_on = false;
-    int bad_batches = 0;              // consecutive batches of short, truncated windows
-    long long seq_stint_len = 32768, seq_stint_left = 32768;
-    bool seq_probe = false;           // the batch of windows in flight is a probe after a sequential stint
-    double win_rate = 0.0, seq_rate_last = 0.0;  // points per millisecond (wall clock) of the last batch / chunk
-
-    // ---- long chains (k_chain_long over the list k_decide keeps) ----
-    long long long_prev = 0;   // Ctl::stat_long at the end of the previous batch
-    bool long_seen = false;    // ... and whether that batch added to it
-    bool long_few = true;      // ... by no more than 64 chains per validation round
-    long long rounds_prev = 0, long_avg = 1;
+    cc::SeqHandover seq;    // the sequential kernel's wall-clock rule (off inside a group)
+    cc::LongChains longs;   // long chains as the previous batch saw them (k_chain_long over the list k_decide keeps)
     long long long_launches = 0;
+
+    // ---- the batch being enqueued: its plan and the views its launches read ----
+    cc::BatchPlan bp{};
+    Table tab{};
+    Rows trows{}, vrows{}, crows{}, vrows_sp{}, crows_sp{}, srows[2] = {};
+    ScanCopy scopy[2] = {};
+    int* long_list = nullptr;       // the list k_decide keeps for the listed long chains and k_claims_heavy
+    int probe_left = 0;             // scans of the batch that still carry the pruned chain's probe
+    hipEvent_t scan_end = nullptr;  // the event recorded right behind the last timed scan (nothing after it yet)
 
     OnlineRun(cc_handle* handle, long long a, long long e, bool no_create_, bool resume_)
         : h(handle), range_a(a), N(e), no_create(no_create_), resume(resume_), c(handle->hc) {}
@@ -175,9 +251,8 @@ struct OnlineRun {
     size_t window_rows() const { return wide() ? 0 : (size_t)win * batch_max; }
     bool seq_g_applies() const { return h->allow_seq_g && h->hc.m_rows >= seq_cap; }
     double seq_rate_guess() const { return cc::seq_rate_guess(h->d, h->hc.m_rows, seq_cap, h->allow_seq_r, h->allow_seq_g); }
-    // (never in a group - every rank has to take the same path, and wall-clock measurements differ -, never with no_create:
-    // the sequential kernels know the reference's loop only)
-    bool seq_possible() const { return seq_mode != 1 && !h->comm.active() && !no_create && (h->hc.m_rows < seq_cap || h->allow_seq_g); }
+    // (`possible` of cc::SeqHandover: never in a group, never with no_create, while the table fits k_seq's image or k_seq_g may run)
+    bool seq_possible() const { return !h->comm.active() && !no_create && (h->hc.m_rows < seq_cap || h->allow_seq_g); }
 
     // lookahead (re)start: the current window is a fresh one (scanned in place), the lookahead scan enqueued next covers
     // the one after it
@@ -197,6 +272,23 @@ struct OnlineRun {
         c.la_cursor[q ^ 1] = 0;
         c.la_b[q ^ 1] = 0;
         c.la_rows[q ^ 1] = 0;
+    }
+
+    // How the batches of windows run - window size, validation rounds, windows per batch, lookahead, dirty scans,
+    // pruned or plain scans, split over the ranks - is decided by cc::WindowPolicy (cc_policy.h) from the device
+    // counters alone; OnlineRun carries the decisions out.  The constants of the call it decides on:
+    cc_policy_config policy_config() const
+    {
+        const ScanPlan& plan = h->scan_plan;
+        cc_policy_config p{};
+        p.window = win; p.rounds_max = R; p.n_end = N; p.d = h->d; p.resume = resume ? 1 : 0;
+        p.windows_per_sync = h->tun.windows_per_sync; p.early_window = h->tun.early_window; p.lookahead = h->tun.lookahead;
+        p.allow_nodirty = h->allow_nodirty ? 1 : 0; p.allow_sparse = h->allow_sparse; p.lookahead_pruned = h->la_pruned ? 1 : 0;
+        p.prune_mode = h->prune_mode; p.prune_applicable = plan.prune_applicable; p.force_prune_rows = plan.force_prune_rows;
+        p.allow_guess = plan.allow_guess; p.allow_probe = plan.allow_probe;
+        p.can_shard = (grouped && !h->shard_suspended) ? 1 : 0;
+        p.shard_min_row_dims = h->shard_min_row_dims; p.shard_min_row_dims_pruned = h->shard_min_row_dims_pruned;
+        return p;
     }
 
     // buffers, control block, policy: everything before the first batch
@@ -224,7 +316,7 @@ struct OnlineRun {
         grouped = h->comm.active();
         if (grouped) {
             // (+ 4: the record behind the last point's carries the rank's pruned-scan sample, see k_merge_partials)
-            // (grids cover at least 64 points, see gw below: the blocks are sized for that even when the window is smaller)
+            // (grids cover at least 64 points, see BatchPlan::gw: the blocks are sized for that even when the window is smaller)
             const size_t gmax = (size_t)std::max(64, h->win_alloc);
             h->gsend_stride = gmax * 4 + 4;
             h->gpart_stride = (size_t)world * (gmax * 4 + 4);
@@ -241,28 +333,7 @@ struct OnlineRun {
         c.n_points = N;
         c.xt_stride = h->n_points;
         c.no_create = no_create ? 1 : 0;
-        // How the batches of windows run - window size, validation rounds, windows per batch, lookahead, dirty scans,
-        // pruned or plain scans, split over the ranks - is decided by cc::WindowPolicy (cc_policy.h) from the device
-        // counters alone; this function carries the decisions out.
-        pcfg.window = win;
-        pcfg.rounds_max = R;
-        pcfg.windows_per_sync = h->tun.windows_per_sync;
-        pcfg.early_window = h->tun.early_window;
-        pcfg.lookahead = h->tun.lookahead;
-        pcfg.allow_nodirty = h->allow_nodirty ? 1 : 0;
-        pcfg.prune_mode = h->prune_mode;
-        pcfg.prune_applicable = plan.prune_applicable;
-        pcfg.can_shard = (grouped && !h->shard_suspended) ? 1 : 0;
-        pcfg.d = h->d;
-        pcfg.resume = resume ? 1 : 0;
-        pcfg.allow_sparse = h->allow_sparse;
-        pcfg.allow_guess = plan.allow_guess;
-        pcfg.allow_probe = plan.allow_probe;
-        pcfg.lookahead_pruned = h->la_pruned ? 1 : 0;
-        pcfg.force_prune_rows = plan.force_prune_rows;
-        pcfg.shard_min_row_dims = h->shard_min_row_dims;
-        pcfg.shard_min_row_dims_pruned = h->shard_min_row_dims_pruned;
-        pcfg.n_end = N;
+        const cc_policy_config pcfg = policy_config();
         const cc_policy_carry pcarry{h->adapt_win, h->clean_batches, h->since_shrink, 0};
         policy.emplace(pcfg, pcarry);
         dec = policy->start(range_a, c.m_rows);
@@ -270,41 +341,10 @@ struct OnlineRun {
         c.win_cfg = dec.win_cfg;
         c.win_b = (int)std::min<long long>(c.win_cfg, N - range_a);
         c.max_rounds = R;
-        c.last_round = 0;
-        c.fc[0] = 0;
-        for (int i = 1; i < CC_MAX_ROUNDS + 2; ++i) c.fc[i] = CC_IDX_INF;
-        c.stat_windows = c.stat_rounds = c.stat_truncated = 0;
-        c.stat_lookahead = 0;
-        c.stat_tiles = c.stat_dirty_tiles = 0;
-        c.stat_unprovable = c.stat_unsafe = 0;
-        c.stat_long = 0;
-        for (int i = 0; i < CC_MAX_ROUNDS + 2; ++i) c.n_long[i] = 0;
-        c.stat_trunc_unknown = 0;
-        c.stat_table_rows = 0;
-        c.stat_seq_points = 0;
-        c.stat_seq_r_points = 0;
-#ifdef CC_LONG_TIMERS
-        for (int i = 0; i < 8; ++i) c.dbg_long[i] = 0;
-#endif
-#ifdef CC_ROUND_DEBUG
-        for (int i = 0; i < CC_MAX_ROUNDS + 2; ++i)
-            for (int q = 0; q < 6; ++q) c.dbg_round[i][q] = 0;
-#endif
-        c.n_heavy = c.n_heavy_new = 0;  // (rows are renumbered between calls: the marks of the last call are void)
-        HIPCHK(hipMemsetAsync(h->tab.heavy.p, 0, h->tab.cap * sizeof(int), h->stream));
-        c.stat_seq_clk = c.stat_seq_wall = 0;
-        c.stat_prune_rows = c.stat_prune_full = 0;
-        c.stat_missed = 0;
-        c.seed_at = -1;
-        for (int q = 0; q < 2; ++q) {
-            c.n_missed[q] = 0;
-            for (int K = 0; K < 2; ++K) { c.tg[q][K] = 0.0; c.tg_ok[q][K] = 0; }
-        }
-        c.cen_absmax = 0ull;            // (k_rebuild_scl takes the table's maximum into it)
+        reset_call_counters(c);
+        HIPCHK(hipMemsetAsync(h->tab.heavy.p, 0, h->tab.cap * sizeof(int), h->stream));  // (the marks behind Ctl::n_heavy)
         c.x_absmax = h->x_absmax;
         set_lookahead(dec.lookahead != 0);
-        c.stat_pair_rows = 0.0;
-        for (int i = 0; i < CC_MAX_ROUNDS + 2; ++i) c.round_hist[i] = 0;
         push_ctl(h);
 
         // no carry set yet: the commit record of an earlier call describes rows that may have moved since
@@ -333,16 +373,9 @@ struct OnlineRun {
 
         done = range_a;
         m_known = c.m_rows;
-        // The sequential kernel (k_seq) for streams on which speculation does not pay: used while the table fits its
-        // LDS image and either the caller forces it or (default) the windows keep being cut short and it measures
-        // faster than they do.  Never inside a multi-GPU group (every rank has to take the same path, and wall-clock
-        // measurements differ between ranks).
-        seq_mode = wide() ? 2 : h->tun.sequential;
+        // the sequential kernel (cc::SeqHandover): forced beyond CC_WINDOW_MAX_DIM, else as the caller's tuning says
         seq_cap = wide() ? 0 : cc_seq_cap_rows(h->d);
-        seq_on = seq_possible() && (seq_mode == 2 || h->seq_sticky);
-        // default policy: the sequential kernel takes over after two batches in a row whose windows were cut short
-        // at a few hundred points; it works in stints (32 k points, doubling), after each of which one batch of
-        // windows is run again and the two measured rates decide who continues
+        seq.start(wide() ? 2 : h->tun.sequential, seq_possible(), h->seq_sticky);
         Rcur = dec.rounds;
         batch_windows = dec.batch_windows;
         h->set_prune(dec.prune);
@@ -356,7 +389,7 @@ struct OnlineRun {
 
     // a stint of the sequential kernel (k_seq): one chunk of points, then back to the windows if the table outgrew its LDS
     // image or the stint is over
-    void sequential_stint(const Table& tab)
+    void sequential_stint()
     {
         const int chunk = 8192;
         const double t0 = now_ms();
@@ -404,18 +437,9 @@ struct OnlineRun {
         if (h->trace)
             fprintf(stderr, "[cc] done %lld rows %d | sequential kernel: %lld points in %.3f ms (so far %lld shader cycles, %.3f ms of kernel time)\n",
                     done, h->hc.m_rows, got, dt, (long long)h->hc.stat_seq_clk, (double)h->hc.stat_seq_wall / 1e5);
-        if (got >= 1024) seq_rate_last = seq_rate;
-        seq_stint_left -= got;
         if (use_g) h->stats.seq_g_points += got;
-        // (k_seq hands back early when its image is full: k_seq_g continues the stint; k_seq_g itself only when the table's
-        // capacity is used up - the windows' loop makes room)
-        const bool full = !seq_possible() || (got < chunk && done < N && (use_g || !h->allow_seq_g));
-        const bool stint_over = seq_mode != 2 && seq_stint_left <= 0;
-        if ((full || stint_over) && done < N && !wide()) {
+        if (seq.after_chunk(got, seq_rate, chunk, use_g, h->allow_seq_g, seq_possible(), done < N, wide()) != cc::SeqHandover::kContinue) {
             // back to the windows: a fresh window at the cursor, no carry set, no pending lookahead scan
-            seq_on = false;
-            seq_probe = stint_over && !full;
-            bad_batches = 0;
             HIPCHK(hipMemsetAsync(h->rec.p, 0, sizeof(CommitRec), h->stream));
             h->hc.win_b = (int)std::min<long long>(h->hc.win_cfg, N - done);
             dec = policy->after_sequential(h->hc.cursor, h->hc.m_rows);
@@ -427,247 +451,258 @@ struct OnlineRun {
         }
     }
 
-    // one batch of windows: per window the snapshot scan (in place or one window ahead on the second stream), round 0 of
-    // the decisions, the validation rounds, the commit - all enqueued without a host round-trip
-    void enqueue_batch(const Table& tab)
+    // what cc::batch_plan decides on: settings, the scan plan, and the control block as last read back
+    cc::BatchInputs batch_inputs() const
     {
-        batch_t0 = now_ms();
-        // pruned snapshot scans for this batch?  (a function of device counters only: every rank decides alike)
+        const ScanPlan& plan = h->scan_plan;
+        cc::BatchInputs in{};
+        in.window = win; in.win_cfg = h->hc.win_cfg; in.batch_windows = batch_windows; in.points_left = N - done;
+        in.S_cfg = S_cfg; in.n_cus = h->n_cus; in.prune_wgs_per_cu = plan.prune_wgs_per_cu; in.plain_wgs_per_cu = plan.plain_wgs_per_cu;
         // (h->prune_now was set for this batch at the end of the previous one, together with the lookahead restart a
         // change of it needs: a pruned scan leaves fewer partials per point than a plain one)
-        const Rows trows{tab.cen, tab.scl, tab.pref, tab.cf1, tab.cf2, tab.w, tab.kind, tab.key, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-        const Rows vrows{ver.cen, ver.scl, ver.pref, ver.cf1, ver.cf2, ver.w, ver.kind, ver.key, ver.next,
-                         ver.tile_dsq, ver.dsq, ver.tau, ver.skip, nullptr, nullptr, nullptr, 0};
-        const Rows crows{car.cen, car.scl, car.pref, car.cf1, car.cf2, car.w, car.kind, car.key, nullptr,
-                         car.tile_dsq, car.dsq, ver.tau, ver.skip_car, nullptr, car.slot, tab.touch, tab.cap};
-        // the sparse dirty scans: the same rows for the round's list of points instead of the window's tiles
-        Rows vrows_sp = vrows, crows_sp = crows;
-        vrows_sp.skip = nullptr; vrows_sp.plist = h->sp_list.p;
-        crows_sp.skip = nullptr; crows_sp.plist = h->sp_list.p;
+        in.prune_now = h->prune_now ? 1 : 0;
+        in.decide_threads = h->decide_threads; in.chain_threads = h->chain_threads; in.commit_threads = h->commit_threads;
+        in.allow_claims = h->allow_claims ? 1 : 0; in.allow_long = h->allow_long ? 1 : 0;
+        in.allow_heavy = h->allow_heavy ? 1 : 0; in.allow_prep = h->allow_prep ? 1 : 0;
+        in.m_rows = h->hc.m_rows; in.n_heavy = h->hc.n_heavy;
+        in.long_seen = longs.seen ? 1 : 0; in.long_few = longs.few ? 1 : 0; in.long_avg = longs.avg;
+        return in;
+    }
+
+    // ---- the launches of a window, each kernel from one place ----
+
+    // the claims of round `round`: T0 and T1 in turn (round 0 writes T0)
+    int* claims_of(int round) const { return (round & 1) ? h->T1.p : h->T0.p; }
+    const ScanCopy& sc_now() const { return scopy[seq_host & 1ull]; }  // the scan copy of this window's parity
+    int quiet_ok() const { return h->allow_quiet ? 1 : 0; }
+    bool sparse_round() const { return nodirty && sparse_now; }
+
+    // the missed points of a guessed-thresholds scan split over ranks (a function of the gathered records: the same list
+    // everywhere) go through the seeded chain on every rank's rows, their new records are exchanged in a second, small
+    // all-gather of fixed size and take the place of the old ones
+    void exchange_missed(hipStream_t st, const Rows& rws, int mode, int round, int q, int srank, int sworld)
+    {
+        launch_scan<false>(h, st, bp.gw, rws, nullptr, h->part.p, bp.S, round, mode, srank, sworld, 1);
+        Cand* const send2 = h->gsend2.p + (size_t)q * CC_MISSED_CAP * 4;
+        Cand* const recv2 = h->gpart2.p + (size_t)q * sworld * CC_MISSED_CAP * 4;
+        hipLaunchKernelGGL(k_merge_partials, dim3((CC_MISSED_CAP + 255) / 256), dim3(256), 0, st, h->ctl.p,
+                           h->part.p, h->part_stride, bp.S, send2, (size_t)0, round, mode,
+                           (const unsigned long long*)nullptr, 0, (const int*)h->missed.p);
+        h->comm.all_gather(send2, recv2, (size_t)CC_MISSED_CAP * 4 * sizeof(Cand), st, st == h->stream2 ? 1 : 0);
+        hipLaunchKernelGGL(k_scatter_missed, dim3((CC_MISSED_CAP * sworld + 255) / 256), dim3(256), 0, st,
+                           (const Ctl*)h->ctl.p, (const int*)h->missed.p, (const Cand*)recv2, sworld,
+                           h->gpart.p, h->gpart_stride, (size_t)bp.gw * 4 + 4, round, mode);
+    }
+
+    // a snapshot scan (mode 0: this window, in place; 1: the window after it, against the scan copy of parity `round`),
+    // timed on request, and in a group the exchange of its records; leaves scan_end
+    void snapshot_scan(hipStream_t st, int mode, int round)
+    {
+        const int gw = bp.gw, S = bp.S;
+        const Rows& rws = (mode == 1) ? srows[round & 1] : trows;
+        h->probe_now = probe_left > 0 && !h->prune_now;  // (the batch's first scan carries the probe)
+        if (h->probe_now) --probe_left;
+        const int srank = shard_on ? myrank : 0, sworld = shard_on ? world : 1;
+        // guessed thresholds with the missed points agreed on from the gathered records: whenever the scan is split
+        // over more than one rank (a group of one rank takes the same steps on request, CHRONOCLUST_HIP_GROUP_GUESS=1:
+        // that is how the second all-gather is exercised over RCCL on one GPU)
+        h->group_guess_now = shard_on && (sworld > 1 || h->group_guess_always);
+        scan_end = nullptr;
+        if (timing) {
+            hipEvent_t a = get_event(h, ev_used), b = get_event(h, ev_used + 1);
+            HIPCHK(hipEventRecord(a, st));
+            launch_scan<false>(h, st, gw, rws, nullptr, h->part.p, S, round, mode, srank, sworld);
+            HIPCHK(hipEventRecord(b, st));
+            timed.push_back({ev_used, h->prune_now ? 1.0 : 0.0});  // (second: a pruned chain or a plain scan)
+            ev_used += 2;
+            if (!shard_on) scan_end = b;
+        } else {
+            launch_scan<false>(h, st, gw, rws, nullptr, h->part.p, S, round, mode, srank, sworld);
+        }
+        if (!shard_on) return;
+        // the rank's S partials per point -> one record per point -> the records of all ranks, in rank
+        // order, in the gathered buffer of the window's parity (what k_decide round 0 reads)
+        const int q = (mode == 1) ? (round & 1) : (int)(seq_host & 1ull);
+        if (timing) HIPCHK(hipEventRecord(get_event(h, ev_used), st));
+        hipLaunchKernelGGL(k_merge_partials, dim3((gw + 255) / 256), dim3(256), 0, st, h->ctl.p, h->part.p,
+                           h->part_stride, S, h->gsend.p, h->gsend_stride, round, mode,
+                           (const unsigned long long*)h->pstat_p(), gw * 4,
+                           (const int*)nullptr);
+        h->comm.all_gather(h->gsend.p + (size_t)q * h->gsend_stride, h->gpart.p + (size_t)q * h->gpart_stride,
+                           ((size_t)gw * 4 + 4) * sizeof(Cand), st, st == h->stream2 ? 1 : 0);
+        if (h->prune_now && h->guess_now && h->group_guess_now && h->lean_now) ++h->stats.scan_lean_launches;
+        if (h->prune_now && h->guess_now && h->group_guess_now && !h->lean_now) exchange_missed(st, rws, mode, round, q, srank, sworld);
+        if (timing) {
+            HIPCHK(hipEventRecord(get_event(h, ev_used + 1), st));
+            timed_comm.push_back(ev_used);
+            ev_used += 2;
+        }
+    }
+
+    // the snapshot scans of a window: its own in place, or - with lookahead - the next window's on the second stream
+    void launch_snapshot_scans(bool first_window)
+    {
+        if (!la_on) return snapshot_scan(sA, 0, 0);
+        // first stream: this window's snapshot scan (enqueued one iteration ago on the second stream)
+        if (evScan) HIPCHK(hipStreamWaitEvent(sA, evScan, 0));
+        // second stream: the snapshot scan of the window after this one, against the scan copy of its
+        // parity (= the table as the previous commit left it), while this window is validated on the first
+        HIPCHK(hipStreamWaitEvent(sB, evCommit, 0));
+        snapshot_scan(sB, 1, (int)((seq_host + 1ull) & 1ull));
+        if (scan_end) evScan = scan_end;  // the timing event already marks the end of the scan: no second record
+        else {
+            evScan = get_sync_event(h, ev_sync++);
+            HIPCHK(hipEventRecord(evScan, sB));
+        }
+        // only the first window of a lookahead batch can need an in-place scan (the device idles the
+        // rest of a batch whose lookahead chain breaks, see Ctl::stall_b)
+        if (first_window && h->hc.mode == 0) snapshot_scan(sA, 0, 0);
+    }
+
+    // k_decide.  Round 0 reads the snapshot candidates alone and carries, as extra workgroups, the previous commit's rows
+    // into the scan copy of this window's parity (cc_apply_carry: the copy was last read by this window's own snapshot
+    // scan, and this window's commit overwrites the carry set); round r > 0 replays against the claims of round r - 1.
+    void launch_decide(int round)
+    {
+        const bool first = round == 0;
+        // where k_decide finds the snapshot candidates of a point
+        const Cand* const dec_part = shard_on ? h->gpart.p : h->part.p;
+        const size_t dec_stride = shard_on ? h->gpart_stride : h->part_stride;
+        const int dec_S = shard_on ? world : bp.S, dec_inner = shard_on ? 1 : bp.S;
+        const size_t dec_outer = shard_on ? (size_t)bp.gw * 4 + 4 : 0;
+        const int dec_tail = (first && shard_on) ? bp.gw * 4 : -1;  // where each rank's pruned-scan sample sits in its block
+        const int ac_blocks = (first && la_on) ? bp.rblocks : 0;
+        const int dirty_mode = (first || !nodirty) ? 0 : (sparse_round() ? 2 : 1);
+        hipLaunchKernelGGL(k_decide, dim3(bp.dblocks + ac_blocks), dim3(h->decide_threads), 0, sA, h->ctl.p, h->X.p, tab, ver, car,
+                           dec_part, dec_stride, h->clean.p, h->dpart.p, h->dpart2.p, h->dseed.p,
+                           first ? (const int*)nullptr : (const int*)claims_of(round - 1), claims_of(round), h->dpath.p, dec_S, Sd,
+                           round, dirty_mode, bp.scan_rows, dec_inner, dec_outer,
+                           first ? (const CommitRec*)h->rec.p : (const CommitRec*)nullptr, first ? sc_now() : ScanCopy{}, ac_blocks,
+                           long_list, bp.long_cap, dec_tail, (!first && round == Rcur) ? 1 : 0, bp.heavy_on ? 1 : 0,
+                           first ? 0 : quiet_ok(), (first && link_now) ? h->link_near.p : (int*)nullptr);
+    }
+
+    // the window's own creators (cc_link.h): points that decided "create" and would be absorbed by an earlier
+    // such point claim the microcluster that one creates - before the first chain replay, not after two of them
+    void launch_link()
+    {
+        launch_link_scan(h, sA, bp.gw);
+        hipLaunchKernelGGL(k_link_apply, dim3((bp.gw + 255) / 256), dim3(256), 0, sA, h->ctl.p, tab, h->T0.p,
+                           (const int*)h->link_near.p, h->dpath.p);
+        ++h->stats.link_launches;
+    }
+
+    // the claims round `round` decided, gathered per microcluster: k_claims while it serves the table, k_claims_heavy for
+    // the heavy rows of a larger one
+    void launch_claims(int round)
+    {
+        if (bp.scan_rows > 0)
+            hipLaunchKernelGGL(k_claims, dim3(bp.scan_rows), dim3(256), 0, sA, h->ctl.p, tab, (const int*)claims_of(round), round,
+                               bp.scan_rows, round ? quiet_ok() : 0);
+    }
+    void launch_claims_heavy(int round)
+    {
+        if (!bp.heavy_on) return;
+        ++h->stats.heavy_launches;
+        hipLaunchKernelGGL(k_claims_heavy, dim3(CC_HEAVY_CAP), dim3(256), 0, sA, h->ctl.p, tab, (const int*)claims_of(round), round,
+                           long_list, bp.long_cap, round ? quiet_ok() : 0);
+    }
+
+    // k_chain_long in the form the plan names (CC_LONG_*: one workgroup per table row or per entry of the round's list; SPLIT:
+    // the large workgroups), as the preparing launch ahead of k_chain (prep_kernel) or as the replay behind it
+    void launch_chain_long(int form, bool prep_kernel, int round)
+    {
+        if (form == CC_LONG_NONE) return;
+        const bool by_list = form == CC_LONG_LIST_SPLIT || form == CC_LONG_LIST_SMALL;
+        const bool split = form == CC_LONG_ROWS_SPLIT || form == CC_LONG_LIST_SPLIT;
+        if (prep_kernel) h->prep_launched = true;
+        else if (by_list) ++long_launches;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(by_list ? bp.long_cap : bp.long_rows), dim3(split ? CC_LONG_THREADS : 256), 0, sA, h->ctl.p,
+                               h->X.p, tab, ver, car, (const int*)claims_of(round - 1), round, by_list ? 0 : bp.long_rows,
+                               by_list ? (const int*)long_list : (const int*)nullptr, bp.prep ? h->lstat.p : nullptr,
+                               bp.prep ? h->lprev.p : nullptr);
+        };
+        if (prep_kernel) launch(k_chain_long<true, true>);
+        else if (split) launch(k_chain_long<true, false>);
+        else launch(k_chain_long<false, false>);
+    }
+
+    void launch_chain(int round)
+    {
+        hipLaunchKernelGGL(k_chain, dim3(bp.cblocks), dim3(h->chain_threads), 0, sA, h->ctl.p, h->X.p, tab, ver, car,
+                           (const int*)claims_of(round - 1), round, bp.long_rows, (const unsigned long long*)(bp.prep ? h->lprev.p : nullptr),
+                           bp.prep ? h->lstat.p : nullptr);
+    }
+
+    void launch_dseed(int round)
+    {
+        hipLaunchKernelGGL(k_dseed, dim3((bp.gw + 63) / 64), dim3(64), 0, sA, h->ctl.p, h->X.p, tab, ver, car,
+                           h->clean.p, h->dseed.p, (const int*)claims_of(round - 1), round, (const int8_t*)h->dpath.p, h->sp_list.p,
+                           sparse_round() ? bp.sparse_cap : 0);
+    }
+
+    // the dirty scans of a round: over the version rows and, with lookahead, the carry set - the window's tiles, or (sparse)
+    // the round's list of points, or not at all while k_dseed rules them out (nodirty)
+    void launch_dirty_scans(int round)
+    {
+        if (nodirty && !sparse_round()) return;
+        const bool sp = nodirty;
+        // (sparse: the grid covers the list's capacity; workgroups beyond the round's count return at once)
+        const int pts = sp ? bp.sparse_cap : bp.gw;
+        launch_scan<true>(h, sA, pts, sp ? vrows_sp : vrows, h->dseed.p, h->dpart.p, Sd, round, 0);
+        if (la_on) launch_scan<true>(h, sA, pts, sp ? crows_sp : crows, h->dseed.p, h->dpart2.p, Sd, round, 1);
+    }
+
+    void launch_commit()
+    {
+        hipLaunchKernelGGL(k_commit_a, dim3(1), dim3(1024), 0, sA, h->ctl.p, tab, ver, car, h->T0.p, h->T1.p,
+                           h->rk.p, h->rec.p, (const Cand*)h->clean.p, (const int8_t*)h->dpath.p);
+        hipLaunchKernelGGL(k_commit_b, dim3(bp.rblocks), dim3(h->commit_threads), 0, sA, h->rec.p, tab, ver, car, h->rk.p, h->dpath.p,
+                           h->lab_uid.p, h->lab_path.p, h->d, sc_now(), h->hc.filter);
+    }
+
+    // one batch of windows: per window the snapshot scan (in place or one window ahead on the second stream), round 0 of
+    // the decisions, the validation rounds, the commit - all enqueued without a host round-trip
+    void enqueue_batch()
+    {
+        batch_t0 = now_ms();
+        bp = cc::batch_plan(batch_inputs());
+        trows = rows_of_table(tab);
+        vrows = rows_of_versions(ver);
+        crows = rows_of_carry(car, ver, tab);
+        vrows_sp = sparse_rows(vrows, h->sp_list.p);
+        crows_sp = sparse_rows(crows, h->sp_list.p);
+        long_list = bp.long_listed ? h->long_list.p : nullptr;
         ev_sync = ev_base;
-        // grids cover the window size of this batch (no window of the batch is larger), not the configured maximum
-        const int gw = std::max(64, std::min(win, h->hc.win_cfg));
-        // partials per point of this batch's clean scans (a pending lookahead scan was launched with the same value:
-        // it only depends on the window size, and a change of that restarts the lookahead chain)
-        // A pruned scan spends a few VALU instructions per row, so a wave must own many rows for its fixed costs
-        // (points, thresholds, tile pipeline, candidate merge: microseconds) not to dominate: as few sub-ranges as fill
-        // the machine once (about a fifth of the plain scan's partials at the full window).
-        const int scan_cus = h->n_cus;
-        const ScanPlan& plan = h->scan_plan;
-        const int S = h->prune_now ? std::max(1, std::min(S_cfg, (scan_cus * plan.prune_wgs_per_cu) / std::max(1, (gw + 63) / 64)))
-                                   : scan_partials_for((gw + 63) / 64, S_cfg, scan_cus * plan.plain_wgs_per_cu);
-        // capacity of the round's list for the sparse dirty scans: a sixteenth of the window (the policy's bound on
-        // the batch's average), in whole tiles
-        const int sparse_cap = std::min(CC_MAX_WINDOW / 16, std::max(64, ((gw / 16 + 63) / 64) * 64));
-        const int decide_threads = h->decide_threads;
-        const int dblocks = (gw + decide_threads / 32 - 1) / (decide_threads / 32);   // one 32-lane group per point
-        const int chain_threads = h->chain_threads;  // 32-lane groups of k_chain per workgroup x 32
-        const int cblocks = (gw + chain_threads / 32 - 1) / (chain_threads / 32);
-        const int commit_threads = h->commit_threads;
-        const int rblocks = std::min((gw + commit_threads / 32 - 1) / (commit_threads / 32), 1024 * (256 / commit_threads));
-        // few MCs: the claims of a window are gathered per MC by k_claims (rows beyond scan_rows, e.g. rows created
-        // during the batch, keep k_decide's atomics)
-        const int scan_rows = (h->allow_claims && h->hc.m_rows > 0 && h->hc.m_rows <= 1024) ? h->hc.m_rows : 0;
-        // ... and their long chains (more than CC_CHAIN_MEMB claimants; k_claims leaves the exact count) are replayed
-        // by k_chain_long, one workgroup per MC, instead of one point after the other
-        const int long_rows = h->allow_long ? scan_rows : 0;
-        // On a larger table long chains are rare on evenly spread data and the rule on skewed data (one population
-        // that takes a third of the events): k_chain_long is launched, over the list k_decide keeps, in the batches
-        // that follow one in which such chains were seen (a function of device counters: every rank decides alike)
-        const bool long_listed = h->allow_long && scan_rows == 0 && long_seen;
-        // heavy rows: their claims are gathered by k_claims_heavy instead of k_decide's atomics from the batch after the
-        // one that marked them (the marks change between windows, on the device; what the host saw at the last sync
-        // decides for the whole batch whether the gathering kernel is launched - k_decide is told the same)
-        const bool heavy_on = h->allow_heavy && scan_rows == 0 && h->hc.n_heavy > 0;
-        int* const long_list = long_listed ? h->long_list.p : nullptr;
-        // workgroups of its launches = entries k_decide may list per round: a few more than the previous batch's
-        // average when that was small (a launch of hundreds of workgroups that return at once is not free)
-        const int long_cap = long_few ? (int)std::min<long long>(CC_LONG_CAP, 2 * long_avg + 8) : CC_LONG_CAP;
         // lookahead scans read a scan copy of the table (see ScanCopy): both in line with the table at the start of
         // a batch, then kept up commit by commit
-        ScanCopy scopy[2] = {ScanCopy{}, ScanCopy{}};
+        scopy[0] = scopy[1] = ScanCopy{};
         if (la_on) scan_copy_sync(h, scopy);
-        Rows srows[2];
-        for (int q = 0; q < 2; ++q)
-            srows[q] = Rows{scopy[q].cen, scopy[q].scl, nullptr, scopy[q].cf1, scopy[q].cf2, scopy[q].w, scopy[q].kind,
-                            scopy[q].key, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+        for (int q = 0; q < 2; ++q) srows[q] = rows_of_scan_copy(scopy[q]);
         evScan = nullptr;  // the scan of the batch's first window is complete (the second stream was drained)
         if (la_on) HIPCHK(hipEventRecord(evCommit, sA));  // everything so far (table, control block) is in place
-        int probe_left = (dec.probe != 0) ? 1 : 0;
-        // No window beyond the end of the range: when windows commit in full, ceil(left / window) of them finish the call (a
-        // window that is cut short leaves its rest to the next batch, as anywhere else).  Every window enqueued past the end
-        // is a dozen launches that find nothing to do - 50-100 us each, up to fifteen of them at the end of every call
-        // (profiles/r06_tool_startup_timeline_before.txt: w36-w47).  A function of counters that are the same on every rank.
-        const int windows_now = (int)std::max<long long>(1, std::min<long long>(batch_windows,
-                                    (N - done + (long long)std::max(1, h->hc.win_cfg) - 1) / (long long)std::max(1, h->hc.win_cfg)));
-        for (int wv = 0; wv < windows_now; ++wv, ++seq_host) {
-            hipEvent_t scan_end = nullptr;  // the event recorded right behind the last timed scan (nothing after it yet)
-            auto timed_scan = [&](hipStream_t st, int mode, int round) {
-                const Rows& rws = (mode == 1) ? srows[round & 1] : trows;
-                h->probe_now = probe_left > 0 && !h->prune_now;  // (the batch's first scan carries the probe)
-                if (h->probe_now) --probe_left;
-                const int srank = shard_on ? myrank : 0, sworld = shard_on ? world : 1;
-                // guessed thresholds with the missed points agreed on from the gathered records: whenever the scan is split
-                // over more than one rank (a group of one rank takes the same steps on request, CHRONOCLUST_HIP_GROUP_GUESS=1:
-                // that is how the second all-gather is exercised over RCCL on one GPU)
-                h->group_guess_now = shard_on && (sworld > 1 || h->group_guess_always);
-                scan_end = nullptr;
-                if (timing) {
-                    hipEvent_t a = get_event(h, ev_used), b = get_event(h, ev_used + 1);
-                    HIPCHK(hipEventRecord(a, st));
-                    launch_scan<false>(h, st, gw, rws, nullptr, h->part.p, S, round, mode, srank, sworld);
-                    HIPCHK(hipEventRecord(b, st));
-                    timed.push_back({ev_used, h->prune_now ? 1.0 : 0.0});  // (second: a pruned chain or a plain scan)
-                    ev_used += 2;
-                    if (!shard_on) scan_end = b;
-                } else {
-                    launch_scan<false>(h, st, gw, rws, nullptr, h->part.p, S, round, mode, srank, sworld);
-                }
-                if (shard_on) {
-                    // the rank's S partials per point -> one record per point -> the records of all ranks, in rank
-                    // order, in the gathered buffer of the window's parity (what k_decide round 0 reads)
-                    const int q = (mode == 1) ? (round & 1) : (int)(seq_host & 1ull);
-                    if (timing) HIPCHK(hipEventRecord(get_event(h, ev_used), st));
-                    hipLaunchKernelGGL(k_merge_partials, dim3((gw + 255) / 256), dim3(256), 0, st, h->ctl.p, h->part.p,
-                                       h->part_stride, S, h->gsend.p, h->gsend_stride, round, mode,
-                                       (const unsigned long long*)h->pstat_p(), gw * 4,
-                                       (const int*)nullptr);
-                    h->comm.all_gather(h->gsend.p + (size_t)q * h->gsend_stride, h->gpart.p + (size_t)q * h->gpart_stride,
-                                       ((size_t)gw * 4 + 4) * sizeof(Cand), st, st == h->stream2 ? 1 : 0);
-                    if (h->prune_now && h->guess_now && h->group_guess_now && h->lean_now) ++h->stats.scan_lean_launches;
-                    if (h->prune_now && h->guess_now && h->group_guess_now && !h->lean_now) {
-                        // guessed thresholds: the points no rank found a pcore MC for (a function of the gathered records:
-                        // the same list everywhere) go through the seeded chain on every rank's rows, their new records
-                        // are exchanged in a second, small all-gather of fixed size and take the place of the old ones
-                        launch_scan<false>(h, st, gw, rws, nullptr, h->part.p, S, round, mode, srank, sworld, 1);
-                        Cand* const send2 = h->gsend2.p + (size_t)q * CC_MISSED_CAP * 4;
-                        Cand* const recv2 = h->gpart2.p + (size_t)q * sworld * CC_MISSED_CAP * 4;
-                        hipLaunchKernelGGL(k_merge_partials, dim3((CC_MISSED_CAP + 255) / 256), dim3(256), 0, st, h->ctl.p,
-                                           h->part.p, h->part_stride, S, send2, (size_t)0, round, mode,
-                                           (const unsigned long long*)nullptr, 0, (const int*)h->missed.p);
-                        h->comm.all_gather(send2, recv2, (size_t)CC_MISSED_CAP * 4 * sizeof(Cand), st, st == h->stream2 ? 1 : 0);
-                        hipLaunchKernelGGL(k_scatter_missed, dim3((CC_MISSED_CAP * sworld + 255) / 256), dim3(256), 0, st,
-                                           (const Ctl*)h->ctl.p, (const int*)h->missed.p, (const Cand*)recv2, sworld,
-                                           h->gpart.p, h->gpart_stride, (size_t)gw * 4 + 4, round, mode);
-                    }
-                    if (timing) {
-                        HIPCHK(hipEventRecord(get_event(h, ev_used + 1), st));
-                        timed_comm.push_back(ev_used);
-                        ev_used += 2;
-                    }
-                }
-            };
-            // where k_decide round 0 finds the snapshot candidates of a point
-            const Cand* const dec_part = shard_on ? h->gpart.p : h->part.p;
-            const size_t dec_stride = shard_on ? h->gpart_stride : h->part_stride;
-            const int dec_S = shard_on ? world : S, dec_inner = shard_on ? 1 : S;
-            const size_t dec_outer = shard_on ? (size_t)gw * 4 + 4 : 0;
-            const int dec_tail = shard_on ? gw * 4 : -1;  // where each rank's pruned-scan sample sits in its block
-            if (la_on) {
-                // first stream: this window's snapshot scan (enqueued one iteration ago on the second stream)
-                if (evScan) HIPCHK(hipStreamWaitEvent(sA, evScan, 0));
-                // second stream: the snapshot scan of the window after this one, against the scan copy of its
-                // parity (= the table as the previous commit left it), while this window is validated on the first
-                HIPCHK(hipStreamWaitEvent(sB, evCommit, 0));
-                timed_scan(sB, 1, (int)((seq_host + 1ull) & 1ull));
-                if (scan_end) evScan = scan_end;  // the timing event already marks the end of the scan: no second record
-                else {
-                    evScan = get_sync_event(h, ev_sync++);
-                    HIPCHK(hipEventRecord(evScan, sB));
-                }
-                // only the first window of a lookahead batch can need an in-place scan (the device idles the
-                // rest of a batch whose lookahead chain breaks, see Ctl::stall_b)
-                if (wv == 0 && h->hc.mode == 0) timed_scan(sA, 0, 0);
-            } else {
-                timed_scan(sA, 0, 0);
-            }
-            // the scan copy of this window's parity was last read by this window's own snapshot scan: first the rows
-            // of the previous commit (cc_apply_carry, extra workgroups of this launch: before this window's commit
-            // overwrites the carry set), then, in k_commit_b, this window's own
-            const ScanCopy sc_now = scopy[seq_host & 1ull];
-            const int ac_blocks = la_on ? rblocks : 0;
-            hipLaunchKernelGGL(k_decide, dim3(dblocks + ac_blocks), dim3(decide_threads), 0, sA, h->ctl.p, h->X.p, tab, ver, car,
-                               dec_part, dec_stride, h->clean.p, h->dpart.p, h->dpart2.p, h->dseed.p, (const int*)nullptr,
-                               h->T0.p, h->dpath.p, dec_S, Sd, 0, 0, scan_rows, dec_inner, dec_outer,
-                               (const CommitRec*)h->rec.p, sc_now, ac_blocks, long_list, long_cap, dec_tail, 0, heavy_on ? 1 : 0, 0,
-                               link_now ? h->link_near.p : (int*)nullptr);
-            if (link_now) {
-                // the window's own creators (cc_link.h): points that decided "create" and would be absorbed by an earlier
-                // such point claim the microcluster that one creates - before the first chain replay, not after two of them
-                launch_link_scan(h, sA, gw);
-                hipLaunchKernelGGL(k_link_apply, dim3((gw + 255) / 256), dim3(256), 0, sA, h->ctl.p, tab, h->T0.p,
-                                   (const int*)h->link_near.p, h->dpath.p);
-                ++h->stats.link_launches;
-            }
-            if (scan_rows > 0)
-                hipLaunchKernelGGL(k_claims, dim3(scan_rows), dim3(256), 0, sA, h->ctl.p, tab, (const int*)h->T0.p, 0, scan_rows, 0);
-            if (heavy_on && ++h->stats.heavy_launches > 0)
-                hipLaunchKernelGGL(k_claims_heavy, dim3(CC_HEAVY_CAP), dim3(256), 0, sA, h->ctl.p, tab, (const int*)h->T0.p, 0,
-                                   long_list, long_cap, 0);
+        probe_left = (dec.probe != 0) ? 1 : 0;
+        for (int wv = 0; wv < bp.windows_now; ++wv, ++seq_host) {
+            launch_snapshot_scans(wv == 0);
+            launch_decide(0);
+            if (link_now) launch_link();
+            launch_claims(0);
+            launch_claims_heavy(0);
             for (int r = 1; r <= Rcur; ++r) {
-                const int* told = ((r - 1) & 1) ? h->T1.p : h->T0.p;
-                int* tnew = (r & 1) ? h->T1.p : h->T0.p;
-                // long chains of pcore MCs: running sums first, by one workgroup per chain; the steps themselves inside k_chain,
-                // the fallback (rejected steps, outlier MCs) behind it
-                // (while the chains are few and long: with 200 table rows a chain is one batch of k_chain_long and the rows' 200
-                // workgroups are parallel enough - the extra launch cost 2 % there, measured)
-                const bool prep = h->allow_prep && ((long_rows > 0 && long_rows <= 64) || (long_listed && long_few));
-                unsigned long long* const lstat = prep ? h->lstat.p : nullptr;
-                unsigned long long* const lprev = prep ? h->lprev.p : nullptr;
-                if (prep) h->prep_launched = true;
-                if (prep && long_rows > 0)
-                    hipLaunchKernelGGL((k_chain_long<true, true>), dim3(long_rows), dim3(CC_LONG_THREADS), 0, sA, h->ctl.p, h->X.p, tab,
-                                       ver, car, told, r, long_rows, (const int*)nullptr, lstat, lprev);
-                else if (prep)
-                    hipLaunchKernelGGL((k_chain_long<true, true>), dim3(long_cap), dim3(CC_LONG_THREADS), 0, sA, h->ctl.p, h->X.p,
-                                       tab, ver, car, told, r, 0, (const int*)long_list, lstat, lprev);
-                hipLaunchKernelGGL(k_chain, dim3(cblocks), dim3(chain_threads), 0, sA,
-                                   h->ctl.p, h->X.p, tab, ver, car, told, r, long_rows, (const unsigned long long*)lprev, lstat);
-                // k_chain_long: one workgroup per table row while k_claims serves the table, else per entry of the
-                // round's list.  The large workgroups (SPLIT) while they are few - rows <= 256, or a short list, judged by
-                // the previous batch's count -, the small ones (two per CU) when hundreds of chains are long
-                if (long_rows > 0 && long_rows <= 256)
-                    hipLaunchKernelGGL((k_chain_long<true, false>), dim3(long_rows), dim3(CC_LONG_THREADS), 0, sA, h->ctl.p, h->X.p, tab,
-                                       ver, car, told, r, long_rows, (const int*)nullptr, lstat, lprev);
-                else if (long_rows > 0)
-                    hipLaunchKernelGGL((k_chain_long<false, false>), dim3(long_rows), dim3(256), 0, sA, h->ctl.p, h->X.p, tab, ver, car,
-                                       told, r, long_rows, (const int*)nullptr, lstat, lprev);
-                else if (long_listed && ++long_launches > 0) {
-                    if (long_few)
-                        hipLaunchKernelGGL((k_chain_long<true, false>), dim3(long_cap), dim3(CC_LONG_THREADS), 0, sA, h->ctl.p, h->X.p,
-                                           tab, ver, car, told, r, 0, (const int*)long_list, lstat, lprev);
-                    else
-                        hipLaunchKernelGGL((k_chain_long<false, false>), dim3(long_cap), dim3(256), 0, sA, h->ctl.p, h->X.p, tab, ver,
-                                           car, told, r, 0, (const int*)long_list, lstat, lprev);
-                }
-                const bool sparse_r = nodirty && sparse_now;
-                hipLaunchKernelGGL(k_dseed, dim3((gw + 63) / 64), dim3(64), 0, sA, h->ctl.p, h->X.p, tab, ver, car,
-                                   h->clean.p, h->dseed.p, told, r, (const int8_t*)h->dpath.p, h->sp_list.p,
-                                   sparse_r ? sparse_cap : 0);
-                if (!nodirty) {
-                    launch_scan<true>(h, sA, gw, vrows, h->dseed.p, h->dpart.p, Sd, r, 0);
-                    if (la_on) launch_scan<true>(h, sA, gw, crows, h->dseed.p, h->dpart2.p, Sd, r, 1);
-                } else if (sparse_r) {
-                    // (the grid covers the list's capacity; workgroups beyond the round's count return at once)
-                    launch_scan<true>(h, sA, sparse_cap, vrows_sp, h->dseed.p, h->dpart.p, Sd, r, 0);
-                    if (la_on) launch_scan<true>(h, sA, sparse_cap, crows_sp, h->dseed.p, h->dpart2.p, Sd, r, 1);
-                }
-                hipLaunchKernelGGL(k_decide, dim3(dblocks), dim3(decide_threads), 0, sA, h->ctl.p, h->X.p, tab, ver, car, dec_part,
-                                   dec_stride, h->clean.p, h->dpart.p, h->dpart2.p, h->dseed.p, told, tnew, h->dpath.p, dec_S, Sd, r, nodirty ? (sparse_r ? 2 : 1) : 0, scan_rows,
-                                   dec_inner, dec_outer, (const CommitRec*)nullptr, ScanCopy{}, 0, long_list, long_cap, -1,
-                                   r == Rcur ? 1 : 0, heavy_on ? 1 : 0, h->allow_quiet ? 1 : 0, (int*)nullptr);
+                if (bp.prep) launch_chain_long(bp.prep_form, true, r);
+                launch_chain(r);
+                launch_chain_long(bp.long_form, false, r);
+                launch_dseed(r);
+                launch_dirty_scans(r);
+                launch_decide(r);
                 // (the claims of the last round are not replayed: nothing to gather either)
-                if (scan_rows > 0 && r < Rcur)
-                    hipLaunchKernelGGL(k_claims, dim3(scan_rows), dim3(256), 0, sA, h->ctl.p, tab, (const int*)tnew, r, scan_rows, h->allow_quiet ? 1 : 0);
-                if (heavy_on && r < Rcur && ++h->stats.heavy_launches > 0)
-                    hipLaunchKernelGGL(k_claims_heavy, dim3(CC_HEAVY_CAP), dim3(256), 0, sA, h->ctl.p, tab, (const int*)tnew, r,
-                                       long_list, long_cap, h->allow_quiet ? 1 : 0);
+                if (r < Rcur) {
+                    launch_claims(r);
+                    launch_claims_heavy(r);
+                }
             }
-            hipLaunchKernelGGL(k_commit_a, dim3(1), dim3(1024), 0, sA, h->ctl.p, tab, ver, car, h->T0.p, h->T1.p,
-                               h->rk.p, h->rec.p, (const Cand*)h->clean.p, (const int8_t*)h->dpath.p);
-            hipLaunchKernelGGL(k_commit_b, dim3(rblocks), dim3(commit_threads), 0, sA, h->rec.p, tab, ver, car, h->rk.p, h->dpath.p,
-                               h->lab_uid.p, h->lab_path.p, h->d, sc_now, h->hc.filter);
+            launch_commit();
             if (la_on) {
                 evCommit = get_sync_event(h, ev_sync++);
                 HIPCHK(hipEventRecord(evCommit, sA));
@@ -683,109 +718,70 @@ struct OnlineRun {
         if (la_on) sync_stream(h, sB);
         seq_host = h->hc.window_seq;
         done = h->hc.cursor;
-        // Round 0 links the points that decide "create" among themselves (cc_link.h: two more small launches per window)
-        // while the batch just read back created a microcluster per 256 points or more - a function of device counters
-        // that are identical on every rank
-        link_now = h->allow_link && !no_create &&
-                   ((long long)(h->hc.m_rows - m_known) * 256 >= std::max<long long>(1, h->hc.cursor - cursor_prev));
+        const double dt = now_ms() - batch_t0;
+        const long long pts_b = h->hc.cursor - cursor_prev;
+        link_now = cc::link_after_batch(h->allow_link && !no_create, h->hc.m_rows - m_known, pts_b);
         m_known = h->hc.m_rows;
+        cursor_prev = h->hc.cursor;
+        longs.after_batch(h->hc.stat_long, h->hc.stat_rounds);
         const bool shard_was = shard_on;
-        {
-            const double dt = now_ms() - batch_t0;
-            const long long pts_b = h->hc.cursor - cursor_prev;
-            if (pts_b > 0) win_rate = (double)pts_b / std::max(dt, 1e-3);
-            cursor_prev = h->hc.cursor;
-            long_seen = h->hc.stat_long > long_prev;
-            // (long chains per window and validation round of the batch: up to 64 count as few)
-            long_avg = (h->hc.stat_long - long_prev) / std::max<long long>(1, h->hc.stat_rounds - rounds_prev) + 1;
-            long_few = long_avg <= 64;
-            long_prev = h->hc.stat_long;
-            rounds_prev = h->hc.stat_rounds;
+        // what the device counted, and the policy's decision for the next batch
+        cc_policy_obs o{};
+        o.cursor = h->hc.cursor;
+        o.m_rows = h->hc.m_rows;
+        o.stall_b = h->hc.stall_b;
+        o.stat_windows = h->hc.stat_windows;
+        o.stat_truncated = h->hc.stat_truncated;
+        o.stat_trunc_unknown = h->hc.stat_trunc_unknown;
+        o.stat_tiles = h->hc.stat_tiles;
+        o.stat_dirty_tiles = h->hc.stat_dirty_tiles;
+        o.stat_unsafe = h->hc.stat_unsafe;
+        o.stat_missed = h->hc.stat_missed;
+        o.tg_ok = (h->hc.tg_ok[0][0] != 0 && h->hc.tg_ok[1][0] != 0) ? 1 : 0;  // (a mean for the pcore kind in both slots)
+        for (int r = 0; r < CC_MAX_ROUNDS + 2; ++r) o.round_hist[r] = h->hc.round_hist[r];
+        o.prune_rows = h->hc.stat_prune_rows;
+        o.prune_full = h->hc.stat_prune_full;
+        dec = policy->after_batch(o);
+        ptrace->batch(o, dec);
+        const cc_policy_carry& k = policy->carry();
+        h->adapt_win = k.adapt_win; h->clean_batches = k.clean_batches; h->since_shrink = k.since_shrink;
+        if (dec.stalled)
+            return fail(h, CC_ERR_INTERNAL, "the online phase made no progress in five consecutive batches of windows");
+        if (h->trace && dec.prune_rows > 0)
+            fprintf(stderr, "[cc] pruned scans of the batch%s (sample): %lld (wave, row) pairs, %.1f %% evaluated in full; points missed by guessed thresholds so far: %lld\n",
+                    h->guess_now ? ", guessed thresholds" : "", (long long)dec.prune_rows,
+                    100.0 * (double)dec.prune_full / (double)dec.prune_rows, (long long)h->hc.stat_missed);
+        pair_rows_eff += (h->hc.stat_pair_rows - pair_rows_prev) / (shard_was ? (double)world : 1.0);
+        if (h->prune_now) pair_rows_pruned += (h->hc.stat_pair_rows - pair_rows_prev) / (shard_was ? (double)world : 1.0);
+        pair_rows_prev = h->hc.stat_pair_rows;
+        if (shard_was) sharded_windows += dec.wins;
+        Rcur = dec.rounds;
+        Sd = Sd_full;
+        nodirty = dec.nodirty != 0;
+        sparse_now = dec.sparse != 0;
+        shard_on = dec.shard != 0;
+        h->set_prune(dec.prune);
+        if (dec.restart) {
+            h->hc.win_cfg = dec.win_cfg;
+            h->hc.win_b = (int)std::min<long long>(dec.win_cfg, N - done);
+            set_lookahead(dec.lookahead != 0);
+            push_ctl_pinned(h);
         }
-        {
-            // what the device counted, and the policy's decision for the next batch
-            cc_policy_obs o{};
-            o.cursor = h->hc.cursor;
-            o.m_rows = h->hc.m_rows;
-            o.stall_b = h->hc.stall_b;
-            o.stat_windows = h->hc.stat_windows;
-            o.stat_truncated = h->hc.stat_truncated;
-            o.stat_trunc_unknown = h->hc.stat_trunc_unknown;
-            o.stat_tiles = h->hc.stat_tiles;
-            o.stat_dirty_tiles = h->hc.stat_dirty_tiles;
-            o.stat_unsafe = h->hc.stat_unsafe;
-            o.stat_missed = h->hc.stat_missed;
-            o.tg_ok = (h->hc.tg_ok[0][0] != 0 && h->hc.tg_ok[1][0] != 0) ? 1 : 0;  // (a mean for the pcore kind in both slots)
-            for (int r = 0; r < CC_MAX_ROUNDS + 2; ++r) o.round_hist[r] = h->hc.round_hist[r];
-            o.prune_rows = h->hc.stat_prune_rows;
-            o.prune_full = h->hc.stat_prune_full;
-            dec = policy->after_batch(o);
-            ptrace->batch(o, dec);
-            const cc_policy_carry& k = policy->carry();
-            h->adapt_win = k.adapt_win; h->clean_batches = k.clean_batches; h->since_shrink = k.since_shrink;
-            if (dec.stalled)
-                return fail(h, CC_ERR_INTERNAL, "the online phase made no progress in five consecutive batches of windows");
-            if (h->trace && dec.prune_rows > 0)
-                fprintf(stderr, "[cc] pruned scans of the batch%s (sample): %lld (wave, row) pairs, %.1f %% evaluated in full; points missed by guessed thresholds so far: %lld\n",
-                        h->guess_now ? ", guessed thresholds" : "", (long long)dec.prune_rows,
-                        100.0 * (double)dec.prune_full / (double)dec.prune_rows, (long long)h->hc.stat_missed);
-            pair_rows_eff += (h->hc.stat_pair_rows - pair_rows_prev) / (shard_was ? (double)world : 1.0);
-            if (h->prune_now) pair_rows_pruned += (h->hc.stat_pair_rows - pair_rows_prev) / (shard_was ? (double)world : 1.0);
-            pair_rows_prev = h->hc.stat_pair_rows;
-            if (shard_was) sharded_windows += dec.wins;
-            Rcur = dec.rounds;
-            Sd = Sd_full;
-            nodirty = dec.nodirty != 0;
-            sparse_now = dec.sparse != 0;
-            shard_on = dec.shard != 0;
-            h->set_prune(dec.prune);
-            if (dec.restart) {
-                h->hc.win_cfg = dec.win_cfg;
-                h->hc.win_b = (int)std::min<long long>(dec.win_cfg, N - done);
-                set_lookahead(dec.lookahead != 0);
-                push_ctl_pinned(h);
-            }
 #ifdef CC_ROUND_DEBUG
-            for (int r = 1; r <= CC_MAX_ROUNDS; ++r)
-                if (h->hc.dbg_round[r][5] != 0)
-                    fprintf(stderr, "[cc]    round %d so far: %llu decisions, %llu refused, create->join new %llu, create->join row %llu, join->create %llu, other MC %llu | windows ended in round %d: %lld\n",
-                            r, h->hc.dbg_round[r][5], h->hc.dbg_round[r][0], h->hc.dbg_round[r][1], h->hc.dbg_round[r][2], h->hc.dbg_round[r][3],
-                            h->hc.dbg_round[r][4], r, (long long)h->hc.round_hist[r]);
+        for (int r = 1; r <= CC_MAX_ROUNDS; ++r)
+            if (h->hc.dbg_round[r][5] != 0)
+                fprintf(stderr, "[cc]    round %d so far: %llu decisions, %llu refused, create->join new %llu, create->join row %llu, join->create %llu, other MC %llu | windows ended in round %d: %lld\n",
+                        r, h->hc.dbg_round[r][5], h->hc.dbg_round[r][0], h->hc.dbg_round[r][1], h->hc.dbg_round[r][2], h->hc.dbg_round[r][3],
+                        h->hc.dbg_round[r][4], r, (long long)h->hc.round_hist[r]);
 #endif
-            if (h->trace)
-                fprintf(stderr, "[cc] %.2f ms done %lld rows %d | batch: %lld windows %lld points trunc %lld (%lld at an undecidable point) lookahead %lld dirty tiles %lld / %lld (points so far: %lld unlocated, %lld unsafe) | next window %d rounds %d\n",
-                        now_ms() - batch_t0, done, h->hc.m_rows, (long long)dec.wins, (long long)dec.pts, (long long)dec.trunc, (long long)dec.unk, (long long)h->hc.stat_lookahead, (long long)dec.dtiles, (long long)dec.tiles,
-                        (long long)h->hc.stat_unprovable, (long long)h->hc.stat_unsafe, dec.want, Rcur);
-            batch_windows = dec.batch_windows;
-            // windows that keep stopping short on a small table: the sequential kernel takes over (and hands back
-            // if it measures slower than this batch did)
-            {
-                const bool bad = dec.bad != 0;
-                bad_batches = bad ? bad_batches + 1 : 0;
-                if (seq_mode == 0 && seq_possible() && done < N) {
-                    if (seq_probe) {
-                        // after a stint: back to the sequential kernel (for twice as long) only if the windows
-                        // are still being cut short and were measurably slower
-                        if (bad && seq_rate_last > 0.0 && win_rate < seq_rate_last) {
-                            seq_on = true;
-                            seq_stint_len = std::min<long long>(seq_stint_len * 2, 1 << 20);
-                        } else {
-                            seq_stint_len = 32768;
-                        }
-                    } else if (bad_batches >= (seq_r_applies() ? 1 : 2) &&
-                               win_rate < (seq_rate_last > 0.0 ? seq_rate_last : seq_rate_guess())) {
-                        // (seq_rate_guess(): what the sequential kernel delivers whatever the data, until it has been
-                        // measured in this call; the short windows of a stream that is merely starting up run faster than
-                        // that.  Where the register kernel applies one such batch is enough: a stint of it costs half of
-                        // what k_seq's costs, and the streams it is built for have a few thousand points per call.)
-                        seq_on = true;
-                    }
-                    if (seq_on) seq_stint_left = seq_stint_len;
-                }
-                seq_probe = false;
-                if (seq_mode == 2 && seq_possible() && done < N) seq_on = true;
-            }
-        }
+        if (h->trace)
+            fprintf(stderr, "[cc] %.2f ms done %lld rows %d | batch: %lld windows %lld points trunc %lld (%lld at an undecidable point) lookahead %lld dirty tiles %lld / %lld (points so far: %lld unlocated, %lld unsafe) | next window %d rounds %d\n",
+                    now_ms() - batch_t0, done, h->hc.m_rows, (long long)dec.wins, (long long)dec.pts, (long long)dec.trunc, (long long)dec.unk, (long long)h->hc.stat_lookahead, (long long)dec.dtiles, (long long)dec.tiles,
+                    (long long)h->hc.stat_unprovable, (long long)h->hc.stat_unsafe, dec.want, Rcur);
+        batch_windows = dec.batch_windows;
+        // the batch's wall-clock rate (none when it committed nothing) against the sequential kernel's: cc::SeqHandover
+        seq.after_batch(dec.bad != 0, pts_b > 0 ? (double)pts_b / std::max(dt, 1e-3) : 0.0, seq_possible(), done < N, seq_r_applies(),
+                        seq_rate_guess());
         return (int)CC_OK;
     }
 
@@ -815,7 +811,7 @@ struct OnlineRun {
         fprintf(stderr, "[cc] k_chain_long, workgroup 0 (shader cycles): collect %llu stage %llu chains %llu step-dim %llu step %llu rows %llu state %llu | batches %llu\n",
                 h->hc.dbg_long[0], h->hc.dbg_long[1], h->hc.dbg_long[2], h->hc.dbg_long[3], h->hc.dbg_long[4], h->hc.dbg_long[5], h->hc.dbg_long[6], h->hc.dbg_long[7]);
 #endif
-        h->seq_sticky = seq_on;
+        h->seq_sticky = seq.on();
         h->stats.table_rows_scanned += h->hc.stat_table_rows;
         h->stats.lookahead_windows += h->hc.stat_lookahead;
         h->stats.pruned_scan_rows += (int64_t)h->hc.stat_prune_rows;
@@ -861,13 +857,13 @@ struct OnlineRun {
     {
         prepare();
         while (done < N) {
-            ensure_table(h, (size_t)m_known + std::max<size_t>(window_rows(), seq_on ? 8192 : 0) + 1);
-            const Table tab = h->tab.view();
-            if (seq_on) {
-                sequential_stint(tab);
+            ensure_table(h, (size_t)m_known + std::max<size_t>(window_rows(), seq.on() ? 8192 : 0) + 1);
+            tab = h->tab.view();
+            if (seq.on()) {
+                sequential_stint();
                 continue;
             }
-            enqueue_batch(tab);
+            enqueue_batch();
             const int rc = after_batch();
             if (rc != CC_OK) return rc;
         }

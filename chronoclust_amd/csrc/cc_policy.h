@@ -10,14 +10,18 @@
 // counters as read back); no clock, no pointer, no HIP.  cc_policy_replay (C-ABI) runs it over recorded observations on
 // a machine without a GPU (tests/test_window_policy.py).
 // The one wall-clock rule of the library - handing a stream of short, truncated windows to the sequential kernel when
-// that measures faster - stays in cc_online_run.h (OnlineRun), is switched off inside a group, and only consumes
-// Decision::bad from here.
+// that measures faster - is SeqHandover below: as pure as the policy, its inputs are Decision::bad and the rates OnlineRun
+// (cc_online_run.h) measures.  Only the clock itself stays outside, in OnlineRun, and the rule is switched off inside a
+// group (wall-clock measurements differ between ranks).  cc_seq_handover_replay (C-ABI) runs it over recorded events.
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <limits>
 
 #include "../../include/chronoclust_hip.h"
+// (the plan of a batch: the other pure half of "how a batch runs".  Whoever includes the policy gets it too, so that
+// cc_host_abi.inc, which exposes both, compiles wherever the policy did)
+#include "cc_batch.h"
 
 namespace cc {
 
@@ -31,7 +35,7 @@ inline bool policy_want_shard(const cc_policy_config& c, int m_rows, bool pruned
 }
 
 // Points per millisecond the sequential kernel that WOULD take over is assumed to manage before it has been measured in
-// this call (the takeover rule of cc_online_run.h compares the windows' measured rate with it).  k_seq_r (rows in registers,
+// this call (SeqHandover below compares the windows' measured rate with it).  k_seq_r (rows in registers,
 // d <= 4) ~0.6 us per point, k_seq (table in LDS) ~1.3 us, whatever the data.  k_seq_g (table in HBM, from `seq_cap` rows
 // on) is one workgroup of 1 024 threads that walks rows / 1 024 rows per thread: 8-14 us per point measured at 150-450
 // rows (profiles/r05_tool_seq_g.txt) - 100 points per ms up to 1 024 rows, and in proportion to 1 024 / rows beyond: at
@@ -334,6 +338,88 @@ private:
     bool prev_probe_ = false;  // the batch that just ran carried a probe
     bool probe_gate_ = false;  // the last batch's table did not grow and most of its tiles were clean: a probe is worth its cost
     bool la_on_ = false, nodirty_ = false, sparse_ = false, shard_on_ = false, prune_on_ = false, first_batch_ = true;
+};
+
+// The sequential kernel (k_seq and its kin) for streams on which speculation does not pay: used while the caller forces
+// it (mode 2) or (mode 0, the default) the windows keep being cut short and it measures faster than they do; mode 1: never.
+// Default rule: the sequential kernel takes over after two batches in a row whose windows were cut short at a few hundred
+// points; it works in stints (32 k points, doubling), after each of which one batch of windows is run again (a probe) and
+// the two measured rates decide who continues.
+// `possible`, everywhere: the sequential kernel may run at all now - never in a group (every rank has to take the same
+// path, and wall-clock measurements differ), never with no_create (the sequential kernels know the reference's loop only),
+// and only while the table fits the LDS image or k_seq_g is allowed.
+class SeqHandover {
+public:
+    enum Chunk { kContinue = 0, kProbe = 1, kWindows = 2 };
+
+    // whether the call starts on the sequential kernel (sticky: the previous call of the handle ended on it)
+    bool start(int mode, bool possible, bool sticky)
+    {
+        seq_mode = mode;
+        seq_on = seq_mode != 1 && possible && (seq_mode == 2 || sticky);
+        return seq_on;
+    }
+
+    // a batch of windows has been read back (bad: Decision::bad; rate: its points per millisecond, <= 0 when it committed
+    // nothing - the last rate stands; more: points are left).  Returns whether the next iteration is a stint.
+    bool after_batch(bool bad, double rate, bool possible, bool more, bool seq_r_applies, double rate_guess)
+    {
+        if (rate > 0.0) win_rate = rate;
+        // windows that keep stopping short on a small table: the sequential kernel takes over (and hands back
+        // if it measures slower than this batch did)
+        bad_batches = bad ? bad_batches + 1 : 0;
+        const bool can = seq_mode != 1 && possible && more;
+        if (seq_mode == 0 && can) {
+            if (seq_probe) {
+                // after a stint: back to the sequential kernel (for twice as long) only if the windows
+                // are still being cut short and were measurably slower
+                if (bad && seq_rate_last > 0.0 && win_rate < seq_rate_last) {
+                    seq_on = true;
+                    seq_stint_len = std::min<long long>(seq_stint_len * 2, 1 << 20);
+                } else {
+                    seq_stint_len = 32768;
+                }
+            } else if (bad_batches >= (seq_r_applies ? 1 : 2) && win_rate < (seq_rate_last > 0.0 ? seq_rate_last : rate_guess)) {
+                // (rate_guess - seq_rate_guess() above: what the sequential kernel delivers whatever the data, until it has
+                // been measured in this call; the short windows of a stream that is merely starting up run faster than
+                // that.  Where the register kernel applies one such batch is enough: a stint of it costs half of
+                // what k_seq's costs, and the streams it is built for have a few thousand points per call.)
+                seq_on = true;
+            }
+            if (seq_on) seq_stint_left = seq_stint_len;
+        }
+        seq_probe = false;
+        if (seq_mode == 2 && can) seq_on = true;
+        return seq_on;
+    }
+
+    // a chunk of `chunk` points has been through the sequential kernel: `got` of them committed, at `rate` points per ms
+    // (use_g: by k_seq_g; wide: more than CC_WINDOW_MAX_DIM dimensions - there are no windows to go back to)
+    Chunk after_chunk(long long got, double rate, long long chunk, bool use_g, bool allow_seq_g, bool possible, bool more, bool wide)
+    {
+        if (got >= 1024) seq_rate_last = rate;
+        seq_stint_left -= got;
+        // (k_seq hands back early when its image is full: k_seq_g continues the stint; k_seq_g itself only when the table's
+        // capacity is used up - the windows' loop makes room)
+        const bool full = !(seq_mode != 1 && possible) || (got < chunk && more && (use_g || !allow_seq_g));
+        const bool stint_over = seq_mode != 2 && seq_stint_left <= 0;
+        if (!((full || stint_over) && more && !wide)) return kContinue;
+        seq_on = false;
+        seq_probe = stint_over && !full;
+        bad_batches = 0;
+        return seq_probe ? kProbe : kWindows;
+    }
+
+    bool on() const { return seq_on; }
+    long long stint_len() const { return seq_stint_len; }
+
+private:
+    int seq_mode = 0;
+    bool seq_on = false;
+    int bad_batches = 0;              // consecutive batches of short, truncated windows
+    long long seq_stint_len = 32768, seq_stint_left = 32768;
+    bool seq_probe = false;           // the batch of windows in flight is a probe after a sequential stint
+    double win_rate = 0.0, seq_rate_last = 0.0;  // points per millisecond (wall clock) of the last batch / chunk
 };
 
 }  // namespace cc

@@ -417,6 +417,61 @@ int cc_policy_replay(const cc_policy_config* cfg, cc_policy_carry* carry, int64_
  * tables beyond the LDS image, slows down in proportion to the rows once they exceed its 1 024 threads.  Pure; < 0 on a
  * bad argument.  No reference counterpart. */
 double cc_policy_seq_rate_guess(int32_t d, int32_t m_rows, int32_t allow_seq_r, int32_t allow_seq_g);
+/* The rule itself (csrc/cc_policy.h, cc::SeqHandover) is pure: the library measures with its clock and hands the rates in.
+ * cc_seq_handover_replay runs it over recorded events - no handle, no GPU, no clock.  outcome[0] / stint_len[0]: whether a call
+ * in `mode` (cc_tuning.sequential; 2 also beyond CC_WINDOW_MAX_DIM) starts on the sequential kernel, and the length of its next
+ * stint; outcome[i + 1] / stint_len[i + 1] after ev[i] - a batch of windows: 1 when the next iteration is a stint of the
+ * sequential kernel; a chunk of the sequential kernel: 0 the stint continues, 1 back to the windows for one batch that is
+ * measured against the stint (a probe), 2 back to the windows for good. */
+typedef struct cc_seq_event {
+    int32_t chunk_event;    /* 0: a batch of windows has been read back, 1: a chunk of the sequential kernel has run            */
+    int32_t bad;            /* batch: cc_policy_decision.bad                                                                */
+    int32_t possible;       /* the sequential kernel may run now: no group, points create, the table fits or k_seq_g is allowed */
+    int32_t more;           /* points of the call are left                                                                  */
+    int32_t seq_r_applies;  /* batch: the register kernel would take over (d = 2 .. 4 and allowed)                           */
+    int32_t use_g;          /* chunk: k_seq_g ran it                                                                        */
+    int32_t allow_seq_g, wide;  /* chunk: k_seq_g is allowed / more than CC_WINDOW_MAX_DIM dimensions (no windows to go back to) */
+    int64_t got, chunk;     /* chunk: points it committed / was given                                                       */
+    double rate;            /* points per millisecond measured: of the batch (<= 0: none, the last one stands) / of the chunk */
+    double rate_guess;      /* batch: cc_policy_seq_rate_guess for the table as it is                                       */
+} cc_seq_event;
+int cc_seq_handover_replay(int32_t mode, int32_t possible, int32_t sticky, const cc_seq_event* ev, int32_t n, int32_t* outcome,
+                           int64_t* stint_len);
+
+/* How one batch of windows is launched (csrc/cc_batch.h; no reference counterpart): grids, partials per point, which kernels
+ * gather the claims and replay the long chains - a pure function of the handle's settings and of what the last read-back of the
+ * control block said, the same on every rank of a group.  cc_batch_plan computes it without a handle or a GPU. */
+typedef struct cc_batch_inputs {
+    int32_t window, win_cfg;   /* the configured window / the window size of this batch (Ctl::win_cfg)                       */
+    int32_t S_cfg;             /* partials per point as configured (segments / waves per workgroup)                          */
+    int32_t n_cus, prune_now;  /* CUs of the device / this batch's snapshot scans are pruned chains                          */
+    int32_t prune_wgs_per_cu, plain_wgs_per_cu;  /* resident workgroups per CU of the scan plan's kernels                    */
+    int32_t decide_threads, chain_threads, commit_threads;
+    int32_t allow_claims, allow_long, allow_heavy, allow_prep;
+    int32_t m_rows, n_heavy;   /* table rows / heavy rows as last read back                                                 */
+    int32_t long_seen, long_few;  /* the previous batch had long chains / no more than 64 per validation round              */
+    int64_t long_avg;          /* ... its average per round, + 1                                                            */
+    int32_t batch_windows, pad;
+    int64_t points_left;
+} cc_batch_inputs;
+enum { CC_LONG_NONE = 0, CC_LONG_ROWS_SPLIT = 1, CC_LONG_ROWS_SMALL = 2, CC_LONG_LIST_SPLIT = 3, CC_LONG_LIST_SMALL = 4 };
+typedef struct cc_batch_geometry {
+    int32_t gw;                /* points the grids cover: the window size of the batch, at least 64                          */
+    int32_t S;                 /* partials per point of the batch's snapshot scans                                          */
+    int32_t sparse_cap;        /* capacity of a round's list for the sparse dirty scans                                      */
+    int32_t dblocks, cblocks, rblocks;  /* workgroups of k_decide, k_chain, k_commit_b                                      */
+    int32_t scan_rows;         /* > 0: k_claims gathers the claims of these table rows                                       */
+    int32_t long_rows;         /* > 0: k_chain_long runs one workgroup per table row                                         */
+    int32_t long_listed;       /* k_chain_long runs over the list k_decide keeps                                            */
+    int32_t heavy_on;          /* k_claims_heavy gathers the claims of the heavy rows                                        */
+    int32_t long_cap;          /* entries k_decide may list per round = workgroups of the listed launches                    */
+    int32_t windows_now;       /* windows to enqueue                                                                        */
+    int32_t prep;              /* k_chain_long<.., PREP> runs ahead of k_chain                                               */
+    int32_t prep_form;         /* ... CC_LONG_ROWS_SPLIT or CC_LONG_LIST_SPLIT (CC_LONG_NONE without prep)                    */
+    int32_t long_form;         /* CC_LONG_*: the k_chain_long launch behind k_chain                                          */
+    int32_t pad;
+} cc_batch_geometry;
+int cc_batch_plan(const cc_batch_inputs* in, cc_batch_geometry* out);
 
 #ifdef __cplusplus
 }

@@ -82,7 +82,8 @@ def test_ctypes_structs_match_the_header_layout(tmp_path):
     pairs = [("cc_params", _lib.CcParams), ("cc_tuning", _lib.CcTuning), ("cc_stats", _lib.CcStats),
              ("cc_relaxed_stats", _lib.CcRelaxedStats), ("cc_policy_config", _lib.CcPolicyConfig),
              ("cc_policy_carry", _lib.CcPolicyCarry), ("cc_policy_obs", _lib.CcPolicyObs),
-             ("cc_policy_decision", _lib.CcPolicyDecision)]
+             ("cc_policy_decision", _lib.CcPolicyDecision), ("cc_seq_event", _lib.CcSeqEvent),
+             ("cc_batch_inputs", _lib.CcBatchInputs), ("cc_batch_geometry", _lib.CcBatchGeometry)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "chronoclust_hip.h"', 'int main(void) {']
     for cname, ctype in pairs:
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))

@@ -1,7 +1,8 @@
 """The pure-host part of the C-ABI library under the sanitizers ("race detection / sanitizers"; CPU only - GPU
 AddressSanitizer is not available on this pool and is never attempted).
 
-csrc/cc_host_abi.inc - the window policy (cc_policy_replay over csrc/cc_policy.h), the per-point text formatter
+csrc/cc_host_abi.inc - the window policy and the sequential hand-over (cc_policy_replay and cc_seq_handover_replay over
+csrc/cc_policy.h), the plan of a batch (cc_batch_plan over csrc/cc_batch.h), the per-point text formatter
 (cc_format_points_csv over csrc/cc_csv.h, called from a pool of host threads), cc_shard_rows and the sequential-kernel rate
 guess: the SAME source text the product's one HIP translation unit includes - is built by g++ as a library of its own
 (tests/host_san/host_abi.cpp) with -fsanitize=address,undefined and with -fsanitize=thread, and driven through the product's
@@ -11,7 +12,8 @@ _lib.load_host_only) in a child interpreter that preloads the sanitizer runtime:
   * every recorded policy trace under tests/golden/policy/ replayed, decisions compared with the recorded ones;
   * the 65 000-value repr corpus of the formatter (specials, uniform, 60 decades, rounded, integral, subnormal) on 1 .. 16
     threads with chunk sizes down to 7 rows, compared with Python's repr;
-  * cc_shard_rows over a grid of (n, world, unit) and its bad-argument paths.
+  * cc_shard_rows over a grid of (n, world, unit) and its bad-argument paths;
+  * every case of tests/test_batch_plan.py (cc_batch_plan, cc_seq_handover_replay).
 
 A sanitizer report makes the child exit non-zero (halt_on_error / abort_on_error) and its text is the failure message."""
 import os
@@ -123,6 +125,16 @@ for bad in ((-1, 1, 0, 1), (10, 0, 0, 1), (10, 2, 2, 1), (10, 2, -1, 1), (10, 2,
         raise AssertionError(bad)
 g = lib.cc_policy_seq_rate_guess
 assert g(20, 10, 1, 1) == 700.0 and g(20, 50000, 1, 1) < 3.0 and g(0, 0, 1, 1) < 0
+# the plan of a batch and the sequential hand-over: every case of tests/test_batch_plan.py
+import test_batch_plan as B
+cases = 0
+for name, fn in sorted(vars(B).items()):
+    if name.startswith("test_") and callable(fn):
+        marks = [m for m in getattr(fn, "pytestmark", []) if m.name == "parametrize"]
+        for args in (marks[0].args[1] if marks else [()]):
+            fn(*args)
+            cases += 1
+assert cases >= 14, cases
 print("HOST-SAN-OK", checked)
 '''
 
