@@ -18,6 +18,7 @@ struct Knobs {
     // lookahead scan a small workgroup finds room on a single SIMD (measured: 4 % per window in steady state)
     // CHRONOCLUST_HIP_CHAIN_THREADS / _DECIDE_THREADS / _COMMIT_THREADS = 64, 128 or 256
     int chain_threads = 64, decide_threads = 256, commit_threads = 256;
+    int decide_group = 16;  // CHRONOCLUST_HIP_DECIDE_GROUP=32: k_decide with one 32-lane group per point whatever d (16, the default: 16-lane groups up to 32 dimensions, 32-lane groups beyond)
     bool allow_scan_u = true;  // k_scan_u where it applies (CHRONOCLUST_HIP_SCANU=0: always k_scan)
     // the pruned snapshot scan (k_seed / k_seed_merge / k_scan_p) where k_scan_u applies and d > 8:
     // CHRONOCLUST_HIP_PRUNE = 0 never, 1 (default) while it pays (the device counts the rows it still evaluates in
@@ -96,6 +97,7 @@ void read_knobs(Knobs& k)
     knob_threads(k.chain_threads, "CHRONOCLUST_HIP_CHAIN_THREADS");
     knob_threads(k.decide_threads, "CHRONOCLUST_HIP_DECIDE_THREADS");
     knob_threads(k.commit_threads, "CHRONOCLUST_HIP_COMMIT_THREADS");
+    { int g = 0; knob_int_in(g, "CHRONOCLUST_HIP_DECIDE_GROUP", 16, 32); if (g == 16 || g == 32) k.decide_group = g; }
     knob_int_in(k.prune_mode, "CHRONOCLUST_HIP_PRUNE", 0, 2);
     knob_int_in(k.prune_rounds4, "CHRONOCLUST_HIP_PRUNE_WGS", 1, 64);
     knob_int_in(k.allow_sparse, "CHRONOCLUST_HIP_SPARSE", 0, INT_MAX);

@@ -573,7 +573,12 @@ struct OnlineRun {
         const int dec_tail = (first && shard_on) ? bp.gw * 4 : -1;  // where each rank's pruned-scan sample sits in its block
         const int ac_blocks = (first && la_on) ? bp.rblocks : 0;
         const int dirty_mode = (first || !nodirty) ? 0 : (sparse_round() ? 2 : 1);
-        hipLaunchKernelGGL(k_decide, dim3(bp.dblocks + ac_blocks), dim3(h->decide_threads), 0, sA, h->ctl.p, h->X.p, tab, ver, car,
+        // lanes per point: 16 while a lane's two dimensions cover the point (d <= 32), else 32.  The grid is derived here -
+        // bp.dblocks counts workgroups at 32 lanes per point -, with the cc_apply_carry workgroups last
+        const int group = (h->d <= 32 && h->decide_group == 16) ? 16 : 32;
+        const int per_wg = h->decide_threads / group;
+        const dim3 grid((bp.gw + per_wg - 1) / per_wg + ac_blocks);
+        hipLaunchKernelGGL(group == 16 ? k_decide<16> : k_decide<32>, grid, dim3(h->decide_threads), 0, sA, h->ctl.p, h->X.p, tab, ver, car,
                            dec_part, dec_stride, h->clean.p, h->dpart.p, h->dpart2.p, h->dseed.p,
                            first ? (const int*)nullptr : (const int*)claims_of(round - 1), claims_of(round), h->dpath.p, dec_S, Sd,
                            round, dirty_mode, bp.scan_rows, dec_inner, dec_outer,

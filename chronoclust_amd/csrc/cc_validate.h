@@ -1,17 +1,21 @@
-// chronoclust_amd/csrc: validation of a window - 32-lane group helpers, k_dseed, k_decide, k_claims, k_chain, k_chain_long, k_commit_a / k_commit_b.  (included by cc_online.h; one translation unit, cc_api.hip)
+// chronoclust_amd/csrc: validation of a window - lane-group helpers, k_dseed, k_decide, k_claims, k_chain, k_chain_long, k_commit_a / k_commit_b.  (included by cc_online.h; one translation unit, cc_api.hip)
 #pragma once
 
 // ---------------------------------------------------------------------------------
-// 32-lane groups: one group per window point in k_decide / k_chain.  Lane l owns dimensions l and l + 32
-// (d <= 64); sums over dimensions stay strictly left to right through an ordered shuffle loop.
+// Lane groups: one group of GW lanes per window point in k_decide (GW = 16 up to 32 dimensions, else 32) / k_chain
+// (32).  Lane l owns dimensions l and l + GW (d <= 2 GW); sums over dimensions stay strictly left to right through
+// an ordered loop over the staged terms.
 // ---------------------------------------------------------------------------------
 
 #define CC_LSTAT_ROWS 1024  // words of `lstat` per round parity: one per workgroup of a k_chain_long launch (table rows <= 1 024, or list entries); two counters behind them
 
+// the ballot of the wave, sliced to the GW bits of this lane's group
+template <int GW = 32>
 __device__ __forceinline__ unsigned cc_group_ballot(bool p)
 {
+    static_assert(GW == 16 || GW == 32, "groups of 16 or 32 lanes");
     const unsigned long long b = __builtin_amdgcn_ballot_w64(p);
-    return (unsigned)(b >> (threadIdx.x & 32));
+    return (unsigned)(b >> (threadIdx.x & (64 - GW))) & (GW == 32 ? 0xFFFFFFFFu : 0xFFFFu);
 }
 
 // Sum over the 32 lanes of a group whose order does not matter (it feeds conservative bounds only), result valid in
@@ -44,20 +48,21 @@ struct GroupAdd {
     int gt1, ne1;                // count(pref' > 1), count(pref' != 1)
 };
 
-// microcluster.py:213-233 + mc_functions.py:45-56, computed by the 32 lanes of a group together.
+// microcluster.py:213-233 + mc_functions.py:45-56, computed by the GW lanes of a group together.
 // Every lane of the group must call it with the same bw / d; b1, b2, px are this lane's two dimensions of the
 // base CF1, CF2 and of the point.
+template <int GW = 32>
 __device__ inline GroupAdd cc_group_add_regs(const double (&b1)[2], const double (&b2)[2], double bw,
                                              const double (&px)[2], int d, const Par& c)
 {
-    const int gl = threadIdx.x & 31;
+    const int gl = threadIdx.x & (GW - 1);
     GroupAdd g;
     const double w1 = bw + 1.0;
     double term[2];
     bool gt[2], ne[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const int i = gl + 32 * h;
+        const int i = gl + GW * h;
         g.c1[h] = 0.0; g.c2[h] = 0.0; g.pr[h] = 1.0; g.cen[h] = 0.0;
         term[h] = 0.0; gt[h] = false; ne[h] = false;
         if (i < d) {
@@ -76,19 +81,20 @@ __device__ inline GroupAdd cc_group_add_regs(const double (&b1)[2], const double
             ne[h] = pr != 1.0;
         }
     }
-    g.gt1 = __builtin_popcount(cc_group_ballot(gt[0])) + __builtin_popcount(cc_group_ballot(gt[1]));
-    g.ne1 = __builtin_popcount(cc_group_ballot(ne[0])) + __builtin_popcount(cc_group_ballot(ne[1]));
-    // ordered sum over dimensions: the terms go through LDS (one 64-double row per group) and every lane adds
-    // them left to right from broadcast reads; the wave owns its rows, so a wavefront fence is enough
-    __shared__ double s_term[(CC_GROUP_THREADS / 32)][64];
-    double* const row = s_term[(threadIdx.x >> 5) % (CC_GROUP_THREADS / 32)];
+    g.gt1 = __builtin_popcount(cc_group_ballot<GW>(gt[0])) + __builtin_popcount(cc_group_ballot<GW>(gt[1]));
+    g.ne1 = __builtin_popcount(cc_group_ballot<GW>(ne[0])) + __builtin_popcount(cc_group_ballot<GW>(ne[1]));
+    // ordered sum over dimensions: the terms go through LDS (one row of 2 GW doubles per group, dimension i at
+    // row[i]) and every lane adds them left to right from broadcast reads; the wave owns its rows, so a wavefront
+    // fence is enough
+    __shared__ double s_term[(CC_GROUP_THREADS / GW)][2 * GW];
+    double* const row = s_term[(threadIdx.x / GW) % (CC_GROUP_THREADS / GW)];
     CC_WAVE_SYNC();
     row[gl] = term[0];
-    row[gl + 32] = term[1];
+    row[gl + GW] = term[1];
     CC_WAVE_SYNC();
     double r2 = 0.0;
-    // mc_functions.py:54, left to right; entries d..63 of the row hold +0.0 (x + 0.0 == x), so the loop runs over
-    // whole groups of eight (four 16-byte LDS reads in flight) without a one-by-one remainder
+    // mc_functions.py:54, left to right; entries d..2 GW - 1 of the row hold +0.0 (x + 0.0 == x), so the loop runs
+    // over whole groups of eight (four 16-byte LDS reads in flight) without a one-by-one remainder
     const int d8 = (d + 7) & ~7;
     for (int i = 0; i < d8; ++i) r2 = r2 + row[i];
     g.r2 = r2;
@@ -96,20 +102,21 @@ __device__ inline GroupAdd cc_group_add_regs(const double (&b1)[2], const double
 }
 
 // the same from memory: bcf1 == nullptr means an empty base
+template <int GW = 32>
 __device__ inline GroupAdd cc_group_add(const double* bcf1, const double* bcf2, double bw, const double* p, int d,
                                         const Par& c)
 {
-    const int gl = threadIdx.x & 31;
+    const int gl = threadIdx.x & (GW - 1);
     double b1[2] = {0.0, 0.0}, b2[2] = {0.0, 0.0}, px[2] = {0.0, 0.0};
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const int i = gl + 32 * h;
+        const int i = gl + GW * h;
         if (i < d) {
             px[h] = p[i];
             if (bcf1) { b1[h] = bcf1[i]; b2[h] = bcf2[i]; }
         }
     }
-    return cc_group_add_regs(b1, b2, bw, px, d, c);
+    return cc_group_add_regs<GW>(b1, b2, bw, px, d, c);
 }
 
 // The same candidate from another lane of this lane's row of 16 (DPP: no trip through the LDS crossbar, which the
@@ -144,6 +151,34 @@ __device__ __forceinline__ void cc_row16_exchanges(F&& f)
 // seed[j*4 + kd*2] = first candidate (slot -1: none), seed[j*4 + kd*2 + 1].dist = cap.
 // ---------------------------------------------------------------------------------
 
+// The three class maxima of a tile_dsq column over its first n records (one wave; every lane ends with the maxima of
+// the records it read, the caller reduces over the lanes).  A record is CC_DSQ_STRIDE words = 32 bytes, read as two
+// 16-byte loads; a lane issues the loads of eight of its records before the first compare, so a window of 49 152
+// points (3 072 records, 48 per lane) costs six round trips to memory, not 48.  The tail is not branched around: a
+// lane whose index runs past the end reads the last record once more, and a maximum does not mind a repeat.
+__device__ __forceinline__ void cc_dsq_window_max(const unsigned long long* __restrict__ tile_dsq, int n,
+                                                  unsigned long long (&m)[3])
+{
+    static_assert(CC_DSQ_STRIDE == 4, "a record is two 16-byte loads");
+    constexpr int AHEAD = 8;
+    const ulonglong2* const rec = reinterpret_cast<const ulonglong2*>(tile_dsq);
+    for (int i0 = threadIdx.x; i0 < n; i0 += 64 * AHEAD) {
+        ulonglong2 a[AHEAD], b[AHEAD];
+#pragma unroll
+        for (int q = 0; q < AHEAD; ++q) {
+            const int i = min(i0 + 64 * q, n - 1);
+            a[q] = rec[(size_t)i * 2];
+            b[q] = rec[(size_t)i * 2 + 1];
+        }
+#pragma unroll
+        for (int q = 0; q < AHEAD; ++q) {
+            m[0] = a[q].x > m[0] ? a[q].x : m[0];
+            m[1] = a[q].y > m[1] ? a[q].y : m[1];
+            m[2] = b[q].x > m[2] ? b[q].x : m[2];
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void k_dseed(Ctl* __restrict__ ctl, const double* __restrict__ X, Table tab,
                                               Versions ver, Carry car, const Cand* __restrict__ clean,
                                               Cand* __restrict__ seed, const int* __restrict__ T, int round,
@@ -161,21 +196,8 @@ __global__ __launch_bounds__(64) void k_dseed(Ctl* __restrict__ ctl, const doubl
     // (per class, see CC_DSQ_STRIDE)
     unsigned long long maxd[3] = {0ull, 0ull, 0ull}, maxd_car[3] = {0ull, 0ull, 0ull};
     {
-        for (int i = threadIdx.x; i < (B + 15) / 16; i += 64) {
-            const unsigned long long* w = ver.tile_dsq + (size_t)i * CC_DSQ_STRIDE;
-            const unsigned long long v0 = w[0], v1 = w[1], v2 = w[2];
-            maxd[0] = v0 > maxd[0] ? v0 : maxd[0];
-            maxd[1] = v1 > maxd[1] ? v1 : maxd[1];
-            maxd[2] = v2 > maxd[2] ? v2 : maxd[2];
-        }
-        if (la_mode)
-            for (int i = threadIdx.x; i < (ctl->car_n + 15) / 16; i += 64) {
-                const unsigned long long* w = car.tile_dsq + (size_t)i * CC_DSQ_STRIDE;
-                const unsigned long long v0 = w[0], v1 = w[1], v2 = w[2];
-                maxd_car[0] = v0 > maxd_car[0] ? v0 : maxd_car[0];
-                maxd_car[1] = v1 > maxd_car[1] ? v1 : maxd_car[1];
-                maxd_car[2] = v2 > maxd_car[2] ? v2 : maxd_car[2];
-            }
+        cc_dsq_window_max(ver.tile_dsq, (B + 15) / 16, maxd);
+        if (la_mode) cc_dsq_window_max(car.tile_dsq, (ctl->car_n + 15) / 16, maxd_car);
 #pragma unroll
         for (int K = 0; K < 3; ++K)
             for (int off = 32; off >= 1; off >>= 1) {
@@ -584,10 +606,16 @@ __device__ __forceinline__ void cc_apply_carry(const CommitRec* __restrict__ rec
 }
 
 // ---------------------------------------------------------------------------------
-// k_decide: one 32-lane group per window point.  Segment partials are merged inside each row of 16 lanes with DPP
-// exchanges (per-point argmin over the MC range), then the reference's decision procedure runs group-uniformly.
+// k_decide<GW>: one group of GW lanes per window point - 16 up to 32 dimensions (a point of 20 dimensions leaves twelve
+// lanes of 32 without any, and the wave count of the launch is what its time follows), 32 beyond.  Segment partials are
+// merged inside each row of 16 lanes with DPP exchanges (per-point argmin over the MC range), then the reference's
+// decision procedure runs group-uniformly.  The groups of a wave go their own ways (stage 0 only, stage 1, refused,
+// beyond the window): every return and every branch below is per group, the DPP exchanges stay inside a row of 16
+// lanes - never wider than a group -, and the one wave-wide operation, the ballot of cc_group_add, is sliced to
+// the group's own bits.
 // ---------------------------------------------------------------------------------
 
+template <int GW>
 __global__ __launch_bounds__(256) void k_decide(Ctl* __restrict__ ctl, const double* __restrict__ X, Table tab,
                                                 Versions ver, Carry car, const Cand* __restrict__ part,
                                                 size_t part_stride, Cand* __restrict__ clean,
@@ -638,8 +666,8 @@ __global__ __launch_bounds__(256) void k_decide(Ctl* __restrict__ ctl, const dou
     // the claims stand, the frontier stays at the window's end (fc[round] was reset when the window was opened), later
     // rounds and the commit see a converged window.
     if (round > 0 && quiet_ok != 0 && ctl->rdiff[round] == 0) return;
-    const int gl = threadIdx.x & 31;
-    const int j = blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5);
+    const int gl = threadIdx.x & (GW - 1);
+    const int j = blockIdx.x * (blockDim.x / GW) + threadIdx.x / GW;
     if (j >= B) return;
     const Par par = cc_load_par(ctl);
     const int d = par.d;
@@ -654,8 +682,8 @@ __global__ __launch_bounds__(256) void k_decide(Ctl* __restrict__ ctl, const dou
         // partial s of point j: one launch wrote S partials per point (part_inner = S, part_outer unused); on the
         // exact multi-GPU path every rank contributed one merged record (part_inner = 1, part_outer = the distance
         // between the ranks' blocks in the gathered buffer)
-        // both rows of 16 lanes of the group merge all S partials (lane l of a row takes l, l + 16, ..), so the two
-        // rows end with the same result and nothing crosses between them
+        // every row of 16 lanes merges all S partials of its point (lane l of a row takes l, l + 16, ..): the two rows
+        // of a 32-lane group end with the same result, and nothing crosses between rows
         for (int s = gl & 15; s < S; s += 16) {
             const Cand* q = part + (size_t)(s / part_inner) * part_outer + ((size_t)j * part_inner + (s % part_inner)) * 4;
             cc_top2_push(p1, p2, q[0]);
@@ -697,6 +725,7 @@ __global__ __launch_bounds__(256) void k_decide(Ctl* __restrict__ ctl, const dou
             dvp = dseed[(size_t)j * 4 + 0];
             dvo = dseed[(size_t)j * 4 + 2];
         } else {
+        // (the first lane of every row of 16: lane 0 of a 16-lane group, lanes 0 and 16 of a 32-lane one)
         if ((gl & 15) == 0 && !(ran && (ran_car || !la_mode))) {
             dvp = dseed[(size_t)j * 4 + 0];
             dvo = dseed[(size_t)j * 4 + 2];
@@ -793,7 +822,7 @@ __global__ __launch_bounds__(256) void k_decide(Ctl* __restrict__ ctl, const dou
             fits = ver.acc[j] != 0;
         }
         if (!known) {
-            const GroupAdd g = cc_group_add(bcf1, bcf2, bw, p, d, par);
+            const GroupAdd g = cc_group_add<GW>(bcf1, bcf2, bw, p, d, par);
             fits = g.r2 <= par.eps_sq;
         }
         if (fits) {
