@@ -47,7 +47,8 @@ class CcStats(C.Structure):
                 ("scan_p2_launches", C.c_int64),
                 ("calib_allgather_us", C.c_double), ("calib_scan_ns_per_row_dim", C.c_double),
                 ("split_threshold_row_dims", C.c_int64), ("split_threshold_row_dims_pruned", C.c_int64),
-                ("missed_plain_launches", C.c_int64), ("seed16_launches", C.c_int64)]
+                ("missed_plain_launches", C.c_int64), ("seed16_launches", C.c_int64),
+                ("pad_rows_launches", C.c_int64)]
 
 
 POLICY_MAX_ROUNDS = 8
@@ -160,6 +161,7 @@ SYMBOLS = {
     "cc_policy_seq_rate_guess": (C.c_double, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "cc_seq_handover_replay": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(CcSeqEvent), C.c_int32, _i32p, _i64p]),
     "cc_batch_plan": (C.c_int, [C.POINTER(CcBatchInputs), C.POINTER(CcBatchGeometry)]),
+    "cc_scan_width": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p]),
     "cc_shard_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p]),
     "cc_set_shard_thresholds": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
 }
@@ -193,7 +195,7 @@ def load():
 
 
 HOST_ONLY_SYMBOLS = ("cc_policy_replay", "cc_policy_seq_rate_guess", "cc_seq_handover_replay", "cc_batch_plan", "cc_shard_rows",
-                     "cc_format_points_csv")
+                     "cc_format_points_csv", "cc_scan_width")
 
 
 def load_host_only(path):
@@ -331,6 +333,19 @@ def batch_plan(**inputs):
     if rc != 0:
         raise ValueError("cc_batch_plan(%r): %s" % (inputs, _ERRORS.get(rc, rc)))
     return {k: getattr(out, k) for k, _ in CcBatchGeometry._fields_ if k != "pad"}
+
+
+SCAN_CHAINS = ("none", "common", "general")  # CC_CHAIN_*
+
+
+def scan_width(d, filter_on, k_pow2):
+    """cc_scan_width: (padded width, k_scan_u serves the plain scan, pruned chain - one of SCAN_CHAINS) for a stream of d
+    dimensions with the pdim filter on or off and k a power of two or not, before any knob (cc::scan_width; no GPU needed)."""
+    padded, scan_u, chain = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = load().cc_scan_width(int(d), int(bool(filter_on)), int(bool(k_pow2)), C.byref(padded), C.byref(scan_u), C.byref(chain))
+    if rc != 0:
+        raise ValueError("cc_scan_width(%r, %r, %r): %s" % (d, filter_on, k_pow2, _ERRORS.get(rc, rc)))
+    return padded.value, bool(scan_u.value), SCAN_CHAINS[chain.value]
 
 
 def shard_rows(n, world, rank, unit=1):

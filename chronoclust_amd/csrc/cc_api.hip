@@ -55,12 +55,13 @@ ScanPlan scan_plan_dp(const cc_handle* h)
 {
     ScanPlan p;
     p.dp = DP;
-    const bool filter = h->hc.filter != 0, pow2 = h->hc.pow2 != 0;
-    // the common case (k a power of two, no pdim filter, no padded dimensions): rows as scalar operands
-    p.scan_u = h->allow_scan_u && !filter && pow2 && h->d == DP;
-    if (p.scan_u && DP > 8) p.chain = ScanPlan::COMMON;
-    else if (h->allow_scan_p3 && h->allow_prune_general && h->d == DP && DP > 8 && DP <= 40 && (filter || !pow2))
-        p.chain = ScanPlan::GENERAL;
+    // which scans exist at this width for this pdim filter and k (cc::scan_width, cc_batch.h), the knobs on top: the common
+    // case (k a power of two, no pdim filter) has the rows as scalar operands - padded ones where d is no compiled width
+    const cc::ScanWidth w = cc::scan_width(h->d, h->hc.filter != 0, h->hc.pow2 != 0);
+    p.scan_u = h->allow_scan_u && w.scan_u;
+    p.pad_rows = p.scan_u && h->d != DP;
+    if (p.scan_u && w.chain == CC_CHAIN_COMMON) p.chain = ScanPlan::COMMON;
+    else if (h->allow_scan_p3 && h->allow_prune_general && w.chain == CC_CHAIN_GENERAL) p.chain = ScanPlan::GENERAL;
     // the window's pruned scan: phase A on the matrix cores (k_scan_p3; GENERAL needs it), two points per lane (k_scan_p2) or
     // one (k_scan_p); CHRONOCLUST_HIP_SCANA: 0 never the split form, 2 always (even over k_scan_p3), 1 from 10 000 table rows
     // on where k_scan_p3 does not run.  The GENERAL chain is never split.
@@ -93,10 +94,16 @@ ScanPlan scan_plan_dp(const cc_handle* h)
 
 ScanPlan scan_plan(const cc_handle* h)
 {
-    // (padded dimensions cost full distance terms: the ladder follows the shapes of BASELINE.json - d = 14, 20, 40)
-    const int d = h->d;
-    return d <= 4 ? scan_plan_dp<4>(h) : d <= 8 ? scan_plan_dp<8>(h) : d <= 14 ? scan_plan_dp<14>(h) : d <= 16 ? scan_plan_dp<16>(h)
-         : d <= 20 ? scan_plan_dp<20>(h) : d <= 32 ? scan_plan_dp<32>(h) : d <= 40 ? scan_plan_dp<40>(h) : scan_plan_dp<64>(h);
+    switch (cc::scan_width(h->d, false, false).padded) {  // (the width is a function of d alone)
+    case 4: return scan_plan_dp<4>(h);
+    case 8: return scan_plan_dp<8>(h);
+    case 14: return scan_plan_dp<14>(h);
+    case 16: return scan_plan_dp<16>(h);
+    case 20: return scan_plan_dp<20>(h);
+    case 32: return scan_plan_dp<32>(h);
+    case 40: return scan_plan_dp<40>(h);
+    default: return scan_plan_dp<64>(h);
+    }
 }
 
 // The clean scan's launches at padded width DP, one helper per kernel family: the window's `win` points, S partials per
@@ -142,7 +149,7 @@ struct ScanCall {
         }
         hipLaunchKernelGGL((k_seed_merge<DP>), dim3((2 * n_pts + 63) / 64), dim3(64), 0, st, h->ctl.p, h->X.p, rows.cen, rows.scl, h->spart.p,
                            h->spart_stride, Sp, h->thr.p, h->thr32.p, h->thr_stride, s16 ? 0.0 : h->prune_F, round, mode, h->cmax.p,
-                           h->pstat_p(), plist);
+                           h->pstat_p(), plist, h->d);
     }
     // k_scan_p3 over the window (behind prefix16()); GENERAL evaluates the pdim filter (lazily, for rows that would enter a
     // list) and divides by k itself
@@ -338,6 +345,36 @@ void launch_scan(cc_handle* h, hipStream_t st, int win, Rows rows, const Cand* c
     }
     throw HipErr{hipErrorInvalidValue, "launch_scan before scan_plan() (OnlineRun::prepare)"};
 #undef CC_SCAN_DP
+}
+
+// The rows of a snapshot scan where d is off the ladder (ScanPlan::pad_rows): k_pad_rows on the scan's stream, right in front
+// of the scan and with its (round, mode), into the mirror of parity q - the window's parity, so that an in-place scan on the
+// first stream and a lookahead scan on the second never share one.  Returns the view the scan chain walks: centroids and
+// operands from the mirror, kinds and keys the source's.  (A full pass per scan, on purpose: nothing that changes the table
+// in place between two scans has to know of the mirror.)
+Rows padded_rows(cc_handle* h, hipStream_t st, Rows rows, int q, int round, int mode)
+{
+    const int dp = h->scan_plan.dp;
+    ensure_pad_rows(h, dp);
+    double* const cen = h->pad_cen.p + (size_t)q * h->pad_stride;
+    double* const scl = h->pad_scl.p + (size_t)q * h->pad_stride;
+    const dim3 grid((unsigned)((h->tab.cap * (size_t)(dp / 2) + 255) / 256));
+#define CC_PAD_DP(DP) hipLaunchKernelGGL((k_pad_rows<DP>), grid, dim3(256), 0, st, (const Ctl*)h->ctl.p, rows.cen, rows.scl, cen, scl, \
+                                         h->d, round, mode); break
+    switch (dp) {
+    case 14: CC_PAD_DP(14);
+    case 16: CC_PAD_DP(16);
+    case 20: CC_PAD_DP(20);
+    case 32: CC_PAD_DP(32);
+    case 40: CC_PAD_DP(40);
+    case 64: CC_PAD_DP(64);
+    default: throw HipErr{hipErrorInvalidValue, "padded_rows: no scan over padded operands at this width"};
+    }
+#undef CC_PAD_DP
+    ++h->stats.pad_rows_launches;
+    rows.cen = cen;
+    rows.scl = scl;
+    return rows;
 }
 
 }  // namespace

@@ -126,11 +126,10 @@ int online_relaxed(cc_handle* h)
             h->rstats.deferred_points += K;
             h->r_didx_all.ensure((size_t)std::max<long long>((long long)W * (b + 1), K));
             HIPCHK(hipMemcpyAsync(h->r_didx_all.p, list.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
-            h->rg_X.ensure((size_t)K * d); h->rg_Xt.ensure((size_t)K * d); h->rg_uid.ensure((size_t)K); h->rg_path.ensure((size_t)K);
+            h->rg_X.ensure((size_t)K * d); h->rg_Xt.ensure((size_t)K * xt_dims(d)); h->rg_uid.ensure((size_t)K); h->rg_path.ensure((size_t)K);
             hipLaunchKernelGGL(k_rel_gather_points, dim3((unsigned)(((size_t)K * d + 255) / 256)), dim3(256), 0, st, h->X.p,
                                h->r_didx_all.p, (int)K, d, h->rg_X.p);
-            hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)(((size_t)K * d + 255) / 256)), dim3(256), 0, st, h->rg_X.p,
-                               h->rg_Xt.p, K, d);
+            HIPCHK(transpose_points_padded(st, h->rg_X.p, h->rg_Xt.p, K, d));  // (the exact run below may scan over padded operands)
             // the gathered points take the place of the resident ones for one exact run
             auto swap_in = [&]() {
                 h->X.swap(h->rg_X);

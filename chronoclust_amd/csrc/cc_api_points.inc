@@ -6,6 +6,22 @@ extern "C" {
 
 static int upload_points(cc_handle* h, const double* x, int64_t n, int32_t d, const double* scale, const double* mn);
 
+// Rows of the dimension-major copy of points of d dimensions: the padded width where a snapshot scan may run over padded
+// operands (9 <= d <= 64, d no compiled width: cc::scan_width) - k_scan_u, k_seed, k_seed16, k_scan_a, k_scan_p, k_scan_p2 and
+// k_scan_p3 read a point's coordinates i < DP of that copy without a bound on d -, else d.  Whatever the pdim filter and k are
+// at the time: they may change between the upload and the run.
+static size_t xt_dims(int d)
+{
+    return (d > 8 && d <= CC_WINDOW_MAX_DIM) ? (size_t)cc::scan_width(d, false, false).padded : (size_t)d;
+}
+// X [n, d] -> Xt [xt_dims(d), n] on `st`: the transpose, then the trailing rows zeroed (zero bytes are +0.0)
+static hipError_t transpose_points_padded(hipStream_t st, const double* X, double* Xt, long long n, int d)
+{
+    const size_t tot = (size_t)n * d, pad = xt_dims(d) - (size_t)d;
+    hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, X, Xt, n, d);
+    return pad > 0 ? hipMemsetAsync(Xt + tot, 0, pad * (size_t)n * 8, st) : hipSuccess;
+}
+
 int cc_points_upload(cc_handle* h, const double* x, int64_t n, int32_t d)
 {
     if (!h || (!x && n > 0) || n < 0) return CC_ERR_BAD_ARG;
@@ -93,7 +109,7 @@ static int upload_points(cc_handle* h, const double* x, int64_t n, int32_t d, co
         }
     }
     h->X.ensure((size_t)n * d);
-    h->Xt.ensure((size_t)n * d);
+    h->Xt.ensure((size_t)n * xt_dims(d));
     h->lab_uid.ensure((size_t)n);
     h->lab_path.ensure((size_t)n);
     h->n_points = n;
@@ -110,8 +126,7 @@ static int upload_points(cc_handle* h, const double* x, int64_t n, int32_t d, co
     }
     int blocks = (int)std::min<long long>((tot + 255) / 256, 4096);
     hipLaunchKernelGGL(k_check_finite, dim3(blocks), dim3(256), 0, h->stream, h->X.p, tot, h->badflag.p);
-    hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->X.p,
-                       h->Xt.p, (long long)n, (int)d);
+    HIPCHK(transpose_points_padded(h->stream, h->X.p, h->Xt.p, (long long)n, (int)d));
     int bad[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(bad, h->badflag.p, 16, hipMemcpyDeviceToHost, h->stream));
     sync_stream(h, h->stream);
@@ -144,7 +159,7 @@ int cc_points_prefetch(cc_handle* h, const double* x, int64_t n, int32_t d, cons
             }
             pf.pin_bytes = chunk;
         }
-        pf.X.ensure((size_t)n * d); pf.Xt.ensure((size_t)n * d); pf.sm.ensure((size_t)2 * d); pf.bad.ensure(4);
+        pf.X.ensure((size_t)n * d); pf.Xt.ensure((size_t)n * xt_dims(d)); pf.sm.ensure((size_t)2 * d); pf.bad.ensure(4);
         pf.active = true;
         const int device = h->device;
         pf.worker = std::thread([&pf, device, chunk]() {
@@ -176,8 +191,7 @@ int cc_points_prefetch(cc_handle* h, const double* x, int64_t n, int32_t d, cons
                 }
                 const int blocks = (int)std::min<long long>((tot + 255) / 256, 4096);
                 hipLaunchKernelGGL(k_check_finite, dim3(blocks), dim3(256), 0, pf.stream, pf.X.p, tot, pf.bad.p);
-                hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, pf.stream, pf.X.p, pf.Xt.p,
-                                   pf.n, pf.d);
+                chk(transpose_points_padded(pf.stream, pf.X.p, pf.Xt.p, pf.n, pf.d), "hipMemsetAsync");
                 chk(hipMemcpyAsync(pf.bad_host, pf.bad.p, 16, hipMemcpyDeviceToHost, pf.stream), "hipMemcpyAsync");
                 chk(hipGetLastError(), "kernel launch");
             }

@@ -22,6 +22,37 @@ using BatchPlan = cc_batch_geometry;
 constexpr int kMaxWindow = 49152;
 constexpr int kLongCap = 512;
 
+// The widths the snapshot scans are compiled for, and which scans serve a stream of d dimensions (pdim filter on or off, k a
+// power of two or not) before any knob is applied - scan_plan() (cc_api.hip) applies those on top; cc_scan_width (C-ABI)
+// answers on a machine without a GPU (tests/test_scan_width_rule.py).
+//   padded   the smallest compiled width >= d (padded dimensions cost full distance terms: the ladder follows the shapes of
+//            BASELINE.json - d = 14, 20, 40); 64 beyond it, where no window runs
+//   scan_u   the plain scan is k_scan_u, the rows as scalar operands: the common case (k a power of two, no pdim filter) at
+//            a compiled width, and from nine dimensions on at any width up to 64 - there the kernels, which index rows as
+//            row * padded, read a padded mirror of the rows (k_pad_rows, cc_scan.h) and points padded with zero rows.
+//            Up to eight dimensions k_scan pads for itself and no pruned chain exists to gain.
+//   chain    the pruned chain: COMMON behind k_scan_u beyond eight dimensions; GENERAL (k_scan_p3<GENERAL>, up to 40
+//            dimensions) where the filter is on or k is not a power of two - at compiled widths only: its phase B evaluates
+//            the pdim filter over the rows at the true d, where a padded dimension would count as preferred
+constexpr int kScanWidths[8] = {4, 8, 14, 16, 20, 32, 40, 64};
+struct ScanWidth {
+    int padded = 0;
+    bool scan_u = false;
+    int chain = CC_CHAIN_NONE;
+};
+inline ScanWidth scan_width(int d, bool filter, bool pow2)
+{
+    ScanWidth w;
+    w.padded = kScanWidths[7];
+    for (int i = 7; i >= 0; --i)
+        if (d <= kScanWidths[i]) w.padded = kScanWidths[i];
+    const bool compiled = d == w.padded, common = !filter && pow2;
+    w.scan_u = common && (compiled || (d > 8 && d < w.padded));
+    if (w.scan_u && w.padded > 8) w.chain = CC_CHAIN_COMMON;
+    else if (!common && compiled && w.padded > 8 && w.padded <= 40) w.chain = CC_CHAIN_GENERAL;
+    return w;
+}
+
 // Partials per point for a batch whose windows have `tiles` point tiles: at most S, not less than S / 2, chosen so that
 // the launch (tiles x S' workgroups) fills whole rounds of the resident workgroups - 1 024 workgroups on a machine that
 // holds 768 at once (d = 40) run as long as 1 536 would.

@@ -146,9 +146,14 @@ struct PinArena {
 // dispatcher, the window policy's configuration and the partial counts).  Two thresholds are in table rows, which grow.
 struct ScanPlan {
     int dp = 0;            // padded dimensionality: the ladder 4 / 8 / 14 / 16 / 20 / 32 / 40 / 64 (0: not planned yet)
-    bool scan_u = false;   // the plain scan is k_scan_u (k a power of two, no pdim filter, d on the ladder), else k_scan<FILTER, POW2>
+    // the plain scan is k_scan_u (k a power of two, no pdim filter; d on the ladder, or 9 <= d <= 64 over padded operands),
+    // else k_scan<FILTER, POW2>.  cc::scan_width (cc_batch.h) is the rule for this and for the chain, before the knobs.
+    bool scan_u = false;
+    // d is off the ladder: every snapshot scan reads the rows' centroids and operands from a mirror at stride dp that
+    // k_pad_rows rebuilds in front of it (padded_rows(), cc_api.hip); the points' dimension-major copy has dp rows
+    bool pad_rows = false;
     // the pruned chain: COMMON where k_scan_u applies and d > 8; GENERAL (k_scan_p3<GENERAL>) where the pdim filter is on or k
-    // is not a power of two
+    // is not a power of two (on the ladder only)
     enum Chain { NONE, COMMON, GENERAL } chain = NONE;
     // its scan of a window: k_scan_p3, k_scan_p2 or k_scan_p - the split form k_scan_a + k_scan_p<MASKED> from split_rows table
     // rows on -; k_scan_p3 LISTED from listed_rows table rows on
@@ -181,7 +186,7 @@ struct BatchScanState {
     }
 };
 
-// buffers of the pruned snapshot scans (sized by ensure_window_buffers, ensure_prefix16 and the dispatcher)
+// buffers of the pruned snapshot scans (sized by ensure_window_buffers, ensure_prefix16, ensure_pad_rows and the dispatcher)
 struct PrunedScanBuffers {
     DevBuf<Cand> probe_part;  // the probe's scratch partials (BatchScanState::probe_now)
     DevBuf<unsigned long long> found;  // [2][CC_MAX_WINDOW / 64] per point tile: the points a guessed-threshold scan found a pcore MC for
@@ -195,6 +200,8 @@ struct PrunedScanBuffers {
     size_t a16_stride = 0;
     DevBuf<unsigned> masks;   // [2][tiles of 128 points, sub-ranges, words per sub-range]  k_scan_a's survivor masks (two window parities)
     size_t mask_stride = 0;
+    DevBuf<double> pad_cen, pad_scl;  // [2][(table capacity + 16) x dp]  k_pad_rows: the scanned rows' centroids / operands at stride dp (two window parities)
+    size_t pad_stride = 0;
     size_t spart_stride = 0, thr_stride = 0;
 };
 
@@ -579,6 +586,22 @@ void ensure_prefix16(cc_handle* h)
     h->a16.ensure(2 * a16_rows * 4);
     h->a16_stride = a16_rows * 4;
     h->hdr16.ensure(2);
+}
+
+// the scanned rows' centroids and operands at the padded stride (k_pad_rows; d off the ladder): two window parities - an
+// in-place scan on the first stream and a lookahead scan on the second can be in flight together.  The scan kernels read
+// rows below the scanned row count only (k_scan_u's request for the next row stays inside its tile, cc_load_prefix and the
+// row walks of the pruned kernels are bounded by their sub-range, k_prefix16's extra rows are rows of its own buffer, not
+// of this one); a tile of rows of slack all the same.  (grown between batches only, like ensure_prefix16)
+void ensure_pad_rows(cc_handle* h, int dp)
+{
+    const size_t stride = (h->tab.cap + CC_SCAN_TM) * (size_t)dp;
+    if (h->pad_stride >= stride) return;
+    sync_stream(h, h->stream);
+    sync_stream(h, h->stream2);
+    h->pad_cen.ensure(2 * stride);
+    h->pad_scl.ensure(2 * stride);
+    h->pad_stride = stride;
 }
 
 hipEvent_t get_event(cc_handle* h, size_t i)

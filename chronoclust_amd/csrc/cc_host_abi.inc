@@ -91,3 +91,13 @@ int cc_batch_plan(const cc_batch_inputs* in, cc_batch_geometry* out)
     return CC_OK;
 }
 
+int cc_scan_width(int32_t d, int32_t filter_on, int32_t k_pow2, int32_t* padded, int32_t* scan_u, int32_t* chain)
+{
+    if (d < 1 || d > CC_MAX_DIM || !padded || !scan_u || !chain) return CC_ERR_BAD_ARG;
+    const cc::ScanWidth w = cc::scan_width(d, filter_on != 0, k_pow2 != 0);
+    *padded = w.padded;
+    *scan_u = w.scan_u ? 1 : 0;
+    *chain = w.chain;
+    return CC_OK;
+}
+

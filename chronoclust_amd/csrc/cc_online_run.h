@@ -499,7 +499,10 @@ struct OnlineRun {
     void snapshot_scan(hipStream_t st, int mode, int round)
     {
         const int gw = bp.gw, S = bp.S;
-        const Rows& rws = (mode == 1) ? srows[round & 1] : trows;
+        const int q = (mode == 1) ? (round & 1) : (int)(seq_host & 1ull);  // the window's parity
+        const Rows& src = (mode == 1) ? srows[round & 1] : trows;
+        // (d off the ladder: the scan, its probe and the relaunch for missed points in a group walk padded operands)
+        const Rows rws = h->scan_plan.pad_rows ? padded_rows(h, st, src, q, round, mode) : src;
         h->probe_now = probe_left > 0 && !h->prune_now;  // (the batch's first scan carries the probe)
         if (h->probe_now) --probe_left;
         const int srank = shard_on ? myrank : 0, sworld = shard_on ? world : 1;
@@ -522,7 +525,6 @@ struct OnlineRun {
         if (!shard_on) return;
         // the rank's S partials per point -> one record per point -> the records of all ranks, in rank
         // order, in the gathered buffer of the window's parity (what k_decide round 0 reads)
-        const int q = (mode == 1) ? (round & 1) : (int)(seq_host & 1ull);
         if (timing) HIPCHK(hipEventRecord(get_event(h, ev_used), st));
         hipLaunchKernelGGL(k_merge_partials, dim3((gw + 255) / 256), dim3(256), 0, st, h->ctl.p, h->part.p,
                            h->part_stride, S, h->gsend.p, h->gsend_stride, round, mode,

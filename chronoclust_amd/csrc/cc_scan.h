@@ -922,6 +922,43 @@ __device__ __forceinline__ ScanWin cc_scan_window(const Ctl* __restrict__ ctl, i
     return w;
 }
 
+// ---------------------------------------------------------------------------------
+// k_pad_rows: the rows of a snapshot scan at the padded stride DP > d.  k_scan_u and the kernels of the pruned chain index a
+// row's centroid and operands as row * DP + i and loop over DP dimensions; where d is not one of the compiled widths they read
+// this mirror of (cen, scl) instead of the table (or the scan copy), rebuilt right in front of every snapshot scan on the scan's
+// stream with the same (round, mode) - both see the same row count and the same rows, whatever sequential stints, injected
+// rows, decay or commits did to the table in between.  A padded dimension holds centroid +0.0 and operand 1.0 ("not preferred":
+// the column holds 1 / pref here, k a power of two); the points' padded coordinates are +0.0 (the dimension-major copy has DP
+// rows, the last DP - d zeroed), so the dimension's term is (0 - 0)^2 * 1 = +0 and the left-to-right sum of non-negative terms
+// is the sum over d dimensions, bit for bit, fused or not.
+// One thread per pair of dimensions of the mirror: consecutive lanes write consecutive 16-byte pairs (DP is even, a row
+// starts on a 16-byte boundary); the reads are the source's rows back to back.  The grid covers the table's capacity, the row
+// count comes from the control block; the mirror's slack rows are neither written nor read.
+// ---------------------------------------------------------------------------------
+template <int DP>
+__global__ __launch_bounds__(256) void k_pad_rows(const Ctl* __restrict__ ctl, const double* __restrict__ g_cen,
+                                                  const double* __restrict__ g_scl, double* __restrict__ m_cen,
+                                                  double* __restrict__ m_scl, int d, int round, int mode)
+{
+    static_assert(DP % 2 == 0, "padded dimensionalities are even");
+    constexpr int HP = DP / 2;
+    const ScanWin win = cc_scan_window(ctl, round, mode);
+    if (win.B == 0) return;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t row = t / HP;
+    if (row >= (size_t)win.rows) return;
+    const int i = 2 * (int)(t % HP);
+    const double* __restrict__ c = g_cen + row * (size_t)d;
+    const double* __restrict__ s = g_scl + row * (size_t)d;
+    double2 vc, vs;
+    vc.x = (i < d) ? c[i] : 0.0;
+    vc.y = (i + 1 < d) ? c[i + 1] : 0.0;
+    vs.x = (i < d) ? s[i] : 1.0;
+    vs.y = (i + 1 < d) ? s[i + 1] : 1.0;
+    *reinterpret_cast<double2*>(m_cen + 2 * t) = vc;
+    *reinterpret_cast<double2*>(m_scl + 2 * t) = vs;
+}
+
 // single-precision pairs: the prefix arithmetic of k_seed and of k_scan_p's phase A runs on packed FP32 instructions
 typedef float cc_f2 __attribute__((ext_vector_type(2)));
 typedef float cc_f4 __attribute__((ext_vector_type(4)));
@@ -1169,7 +1206,8 @@ __global__ __launch_bounds__(64) void k_seed_merge(const Ctl* __restrict__ ctl, 
                                                    const SeedCand* __restrict__ spart, size_t spart_stride, int S,
                                                    double* __restrict__ thr, float* __restrict__ thr32, size_t thr_stride,
                                                    double F, int round, int mode, const unsigned long long* __restrict__ cmax,
-                                                   unsigned long long* __restrict__ pstat, const int* __restrict__ plist)
+                                                   unsigned long long* __restrict__ pstat, const int* __restrict__ plist,
+                                                   int xd)
 {
     const ScanWin win = cc_scan_window(ctl, round, mode);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1183,12 +1221,14 @@ __global__ __launch_bounds__(64) void k_seed_merge(const Ctl* __restrict__ ctl, 
         // the sample counters of this window's k_scan_p (split scans only: see there) start at zero
         if (t < 2) pstat[win.q * 2 + t] = 0ull;
     }
-    constexpr int d = DP;  // (the pruned scan runs for d == DP only: every loop below unrolls, its loads go out together)
+    // (the rows at stride DP - the table's where d == DP, k_pad_rows' mirror else -: every loop below unrolls, its loads go out
+    // together.  The point comes from the row-major copy, whose rows hold xd <= DP coordinates: zero beyond them.)
+    constexpr int d = DP;
     const bool pow2 = ctl->pow2 != 0;
     spart += (size_t)win.q * spart_stride;
     thr += (size_t)win.q * thr_stride;
     thr32 += (size_t)win.q * thr_stride;
-    const double* p = X + (size_t)(win.cursor + j) * d;
+    const double* p = X + (size_t)(win.cursor + j) * xd;
     float b0 = __builtin_inff(), b1 = __builtin_inff(), b2 = __builtin_inff();
     int i0 = -1, i1 = -1, i2 = -1;
     for (int s = 0; s < S; ++s) {
@@ -1209,7 +1249,7 @@ __global__ __launch_bounds__(64) void k_seed_merge(const Ctl* __restrict__ ctl, 
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int i = (i0 + u < d) ? i0 + u : d - 1;
-                pv[u] = p[i];
+                pv[u] = (i < xd) ? p[i] : 0.0;
                 c0[u] = g_cen[o0 + i]; c1[u] = g_cen[o1 + i]; c2[u] = g_cen[o2 + i];
                 s0[u] = g_scl[o0 + i]; s1[u] = g_scl[o1 + i]; s2[u] = g_scl[o2 + i];
             }

@@ -151,6 +151,7 @@ typedef struct cc_stats {
     int64_t split_threshold_row_dims_pruned;
     int64_t missed_plain_launches; /* plain scans (k_scan_u over a point list) for the points a guessed-threshold scan missed */
     int64_t seed16_launches;       /* seeded pruned chains whose seeds came from the matrix cores (k_seed16) with the tight threshold */
+    int64_t pad_rows_launches;     /* snapshot scans that ran over padded operands (k_pad_rows in front of them: 9 <= d <= 64, d no compiled width) */
 } cc_stats;
 
 /* HDDStream.__init__ (hddstream.py:30-67): one state object on GPU `device`. */
@@ -472,6 +473,14 @@ typedef struct cc_batch_geometry {
     int32_t pad;
 } cc_batch_geometry;
 int cc_batch_plan(const cc_batch_inputs* in, cc_batch_geometry* out);
+
+/* Which snapshot scans serve a stream of d dimensions (csrc/cc_batch.h, cc::scan_width; no reference counterpart), before any
+ * CHRONOCLUST_HIP_* knob: the width the scan kernels run at (the smallest compiled one >= d: 4, 8, 14, 16, 20, 32, 40, 64),
+ * whether the plain scan is the scalar-operand kernel (k a power of two, no pdim filter; at a compiled width, or from nine
+ * dimensions on over padded operands) and which pruned chain exists.  No handle, no GPU.  CC_ERR_BAD_ARG unless
+ * 1 <= d <= CC_MAX_DIM. */
+enum { CC_CHAIN_NONE = 0, CC_CHAIN_COMMON = 1, CC_CHAIN_GENERAL = 2 };
+int cc_scan_width(int32_t d, int32_t filter_on, int32_t k_pow2, int32_t* padded, int32_t* scan_u, int32_t* chain);
 
 #ifdef __cplusplus
 }
