@@ -61,7 +61,10 @@ ScanPlan scan_plan_dp(const cc_handle* h)
     p.scan_u = h->allow_scan_u && w.scan_u;
     p.pad_rows = p.scan_u && h->d != DP;
     if (p.scan_u && w.chain == CC_CHAIN_COMMON) p.chain = ScanPlan::COMMON;
-    else if (h->allow_scan_p3 && h->allow_prune_general && w.chain == CC_CHAIN_GENERAL) p.chain = ScanPlan::GENERAL;
+    // (no pruned chain on a tainted handle: phase A bounds a row's distance from below with min(1, 1 / k) as the smallest weight
+    // of a dimension, phase B divides by the stored entry - one above max(k, 1) weighs less, and "abandoned implies beyond T"
+    // no longer holds.  Taint has cleared pow2, so the common chain is gone already.)
+    else if (h->allow_scan_p3 && h->allow_prune_general && !h->tainted && w.chain == CC_CHAIN_GENERAL) p.chain = ScanPlan::GENERAL;
     // the window's pruned scan: phase A on the matrix cores (k_scan_p3; GENERAL needs it), two points per lane (k_scan_p2) or
     // one (k_scan_p); CHRONOCLUST_HIP_SCANA: 0 never the split form, 2 always (even over k_scan_p3), 1 from 10 000 table rows
     // on where k_scan_p3 does not run.  The GENERAL chain is never split.

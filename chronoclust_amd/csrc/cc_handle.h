@@ -284,7 +284,11 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
     DevBuf<Ctl> ctl;
     // a pruned scan's sample {rows visited, rows completed} per window parity: Ctl::pstat, as the kernels take it
     unsigned long long* pstat_p() const { return (unsigned long long*)((char*)ctl.p + offsetof(Ctl, pstat)); }
-    bool tainted = false;  // a pref value outside {1, k} may be present -> never take the x * (1/k) shortcut
+    // a stored preference entry outside {1, k} may be present (cc_set_params with another k on a table that holds rows,
+    // cc_inject_mc / cc_inject_bulk; cleared by cc_reset).  Two consequences: never the x * (1/k) shortcut (Ctl::pow2 = 0,
+    // refresh_ctl_params), and no pruned chain (scan_plan, cc_api.hip): the prefix bounds of cc_tau16, cc_tau32 and cc_thr32
+    // take min(1, 1 / k) for the smallest weight of a dimension, which a stored entry above max(k, 1) undercuts
+    bool tainted = false;
     int adapt_win = 0;      // window size the last call settled at (0: none yet)
     int clean_batches = 0;  // consecutive batches without a truncated window
     int since_shrink = 1000;  // batches since the window was last shrunk

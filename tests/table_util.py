@@ -299,20 +299,19 @@ def same_lists(h, o, what=""):
     assert h.counters() == o.counters, "%s counters %r / %r" % (what, h.counters(), o.counters)
 
 
-def group_offline(world, par, pcores, device=0):
-    """The offline phase of `world` handles of one in-process group (the row-sharded path forced on from the first row),
-    one host thread per rank: [(info, clusters)] by rank."""
+def _run_group(world, work, device=0):
+    """`world` handles of one in-process group, work(handle, rank) on one host thread per rank.  A rank that fails leaves the
+    group, so that its peers do not wait for it; the first error is raised after the join, the handles closed.  Returns
+    (the handles - the caller closes them -, what work returned by rank)."""
     from chronoclust_amd import _lib
     hs = [_lib.Handle(device) for _ in range(world)]
     try:
         _lib.comm_init_local(hs)
         results, errors = [None] * world, [None] * world
 
-        def work(rank):
+        def run(rank):
             try:
-                hs[rank].set_shard_thresholds(0, 0)
-                fill_handle(hs[rank], par, pcores)
-                results[rank] = handle_offline(hs[rank])
+                results[rank] = work(hs[rank], rank)
             except BaseException as e:  # noqa: BLE001 - reported after the join
                 errors[rank] = e
                 try:
@@ -320,7 +319,7 @@ def group_offline(world, par, pcores, device=0):
                 except Exception:
                     pass
 
-        threads = [threading.Thread(target=work, args=(r,)) for r in range(world)]
+        threads = [threading.Thread(target=run, args=(r,)) for r in range(world)]
         for th in threads:
             th.start()
         for th in threads:
@@ -328,10 +327,25 @@ def group_offline(world, par, pcores, device=0):
         for e in errors:
             if e is not None:
                 raise e
-        return results
-    finally:
+        return hs, results
+    except BaseException:
         for h in hs:
             h.close()
+        raise
+
+
+def group_offline(world, par, pcores, device=0):
+    """The offline phase of `world` handles of one in-process group (the row-sharded path forced on from the first row),
+    one host thread per rank: [(info, clusters)] by rank."""
+    def work(h, rank):
+        h.set_shard_thresholds(0, 0)
+        fill_handle(h, par, pcores)
+        return handle_offline(h)
+
+    hs, results = _run_group(world, work, device)
+    for h in hs:
+        h.close()
+    return results
 
 
 # ---- structure checks: conditions on the inputs, on the oracle's own output -----------------------------------------
@@ -416,12 +430,515 @@ def build_table(name):
     return gen(**kw)
 
 
+# ---- the online phase on injected tables ------------------------------------------------------------------------------
+#
+# A streamed table always agrees with itself: stored preference entries are k or 1 as the row's CF1 / CF2 and the current k
+# say, the table is never larger than the points seen, and list position follows creation time.  The generators below
+# build both lists directly, give them to handle and oracle alike and send points through
+#     make_oracle(par, pcores, outliers).online_microcluster_maintenance(X, 0, reset_param=False, offline=False)
+# (no decay, no parameter derivation) on one side and fill_handle + Handle.online(X) on the other.  Each returns
+# (pcores, outliers, params, X, meta); `check_online` asserts on the ORACLE's result that what the case exists for happened.
+
+def _sites(rng, n, d, sep, lo=0.1, hi=0.9):
+    """n points of [lo, hi)^d.  Up to 1 500 of them are drawn one at a time, pairwise at least `sep` apart; larger sets
+    are only used where d makes a closer pair improbable (the structure checks notice one)."""
+    if n > 1500:
+        return rng.uniform(lo, hi, (n, d))
+    out = np.empty((n, d))
+    i = tries = 0
+    while i < n:
+        c = rng.uniform(lo, hi, d)
+        tries += 1
+        assert tries < 200 * n + 1000, "no room for %d sites %g apart in %d dimensions" % (n, sep, d)
+        if i == 0 or ((out[:i] - c) ** 2).sum(axis=1).min() >= sep * sep:
+            out[i] = c
+            i += 1
+    return out
+
+
+def _unit(rng, n, d, first=None):
+    """n random unit vectors of d dimensions, zero beyond the first `first` of them."""
+    u = np.zeros((n, d))
+    f = d if first is None else min(d, first)
+    u[:, :f] = rng.normal(size=(n, f))
+    return u / np.sqrt((u * u).sum(axis=1))[:, None]
+
+
+def _outlier_table(rng, cen, var, pref, w, first=2_000_000):
+    ids = _ids(rng, len(w), first)
+    return Table(cen, var, pref, w, ids, ids)            # (an outlier's id is its uid)
+
+
+def tentative(t, rows, x, par):
+    """(pdim, projected radius) of rows `rows` of a table after the tentative add of the points x [len(rows), d]: the
+    reference's expressions (cf2 / w - (cf1 / w)^2, entry k where that is <= delta_sq) in numpy."""
+    w = (t.w[rows] + 1.0)[:, None]
+    var = (t.cf2[rows] + x * x) / w - ((t.cf1[rows] + x) / w) ** 2
+    pref = np.where(var <= par.delta_sq, par.k, 1.0)
+    return (pref != 1.0).sum(axis=1), (var / pref).sum(axis=1)
+
+
+def victims(seed, pairs, d, k=4.0, stored=None, on_outliers=False, filt=False, D=0.05, points=None):
+    """Taint: pairs of rows (R, R2), the pairs at least 4 D apart, one point p per pair.  R holds `stored` (>= 256 max(k, 1),
+    by default 4 096 max(k, 1)) in every stored entry and lies at Euclidean distance D from p, the offset within the first
+    eight dimensions (all of them part of every prefix test); R2 holds entries of 1 and lies at distance E, E^2 = 4 D^2 /
+    stored.  The reference's distances are D^2 / stored to R and 4 D^2 / stored to R2: R wins.  A bound that takes
+    min(1, 1 / k) for the smallest weight of a dimension puts R at D^2 / max(k, 1) or more - beyond 16 x either distance.
+    Coordinates stay within [0, 1) and D is 0.05, so that half-precision prefixes resolve the offset (2^-11 of the range a
+    coordinate).  A join recomputes the entries with the current k, so every R is hit once.  Weights 10, variances up to
+    1e-8, eps 0.05: the tentative radius is D^2 10 / 121 at most.
+    on_outliers: the rows on the outlier list (beta mu = 2: every join promotes), a few far pcores beside them.
+    filt: pi = d - 3; R and R2 carry three dimensions of variance 4 delta_sq (delta_sq 4e-5 keeps the radius below eps_sq),
+    and a third row R3 per pair - entries 1, every variance tiny, E / 4 from p - is nearer than R and rejected by the
+    filter (its tentative pdim is d).  points: only so many of the pairs get their point."""
+    rng = np.random.default_rng(seed)
+    stored = float(stored) if stored else 4096.0 * max(k, 1.0)
+    assert stored >= 256.0 * max(k, 1.0)
+    nw = 3 if filt else 0
+    delta_sq = 4e-5 if filt else 0.05 ** 2
+    n_decoy = max(1, pairs // 8) if on_outliers else 0
+    sites = _sites(rng, pairs + n_decoy, d, 4.0 * D)
+    cR = sites[:pairs]
+    X = cR + D * _unit(rng, pairs, d, first=8)
+    E = 2.0 * D / np.sqrt(stored)
+    cens = [cR, X + E * _unit(rng, pairs, d)] + ([X + 0.25 * E * _unit(rng, pairs, d)] if filt else [])
+    prefs = [np.full((pairs, d), stored), np.ones((pairs, d))] + ([np.ones((pairs, d))] if filt else [])
+    var = rng.uniform(0.0, 1e-8, (len(cens) * pairs, d))
+    for r in range(2 * pairs if filt else 0):
+        var[r, rng.choice(d, nw, replace=False)] = 4.0 * delta_sq
+    m = len(cens) * pairs
+    perm = rng.permutation(m)
+    pos_of = np.empty(m, np.int64)
+    pos_of[perm] = np.arange(m)
+    cen, pref, var = np.concatenate(cens)[perm], np.concatenate(prefs)[perm], var[perm]
+    w = np.full(m, 10.0)
+    if on_outliers:
+        rows = _outlier_table(rng, cen, var, pref, w)
+        pcores = _table(rng, sites[pairs:], rng.uniform(0.0, 1e-8, (n_decoy, d)),
+                        np.where(rng.random((n_decoy, d)) < 0.5, k, 1.0), np.full(n_decoy, 10.0))
+        outliers = rows
+    else:
+        rows = _table(rng, cen, var, pref, w)
+        pcores, outliers = rows, None
+    order = rng.permutation(pairs)[:points]               # the points in an order of their own
+    par = Params(0.05 ** 2, delta_sq, k, 0.5, 4.0, 0.1, 0.5, 0.25, 0.05, d - nw)
+    meta = dict(kind="victims", tainted=True, on_outliers=on_outliers, filt=filt, rows=rows, pair=order,
+                R=pos_of[:pairs], R2=pos_of[pairs:2 * pairs], R3=pos_of[2 * pairs:] if filt else None)
+    return pcores, outliers, par, np.ascontiguousarray(X[order]), meta
+
+
+def victims_by_set_params(seed, pairs, d, k=4.0, k_first=4096.0, D=0.05):
+    """The same pairs with nothing injected: a first call with k = k_first (a power of two, >= 256 max(k, 1)) builds the
+    rows from points - per pair ten points c2 +- v (|v_i| = 1e-4 > delta = 5e-5: entries of 1), then forty points on cR
+    (variance 0: entries of k_first) -, then k is lowered on handle and oracle alike (meta["first"] holds the first call's
+    parameters and points) and the victim points follow.  eps_sq is 1e-4: a point D from a row of weight 10 fails its radius
+    test (D^2 10 / 121 = 2.1e-4), which keeps R's points out of R2; a point D from a row of weight 40 passes
+    (D^2 40 / 1 681 = 5.9e-5), which lets the victim join R.  beta mu = 4: both rows are pcores after four points."""
+    rng = np.random.default_rng(seed)
+    assert k_first >= 256.0 * max(k, 1.0)
+    cR = _sites(rng, pairs, d, 4.0 * D)
+    X = cR + D * _unit(rng, pairs, d, first=8)
+    c2 = X + 2.0 * D / np.sqrt(k_first) * _unit(rng, pairs, d)
+    v = 1e-4 * np.where(rng.random((pairs, d)) < 0.5, -1.0, 1.0)
+    sign = np.tile(np.array([1.0, -1.0]), 5)
+    pts2 = (c2[:, None, :] + sign[None, :, None] * v[:, None, :]).reshape(pairs * 10, d)
+    own2 = np.repeat(np.arange(pairs), 10)
+    o2 = rng.permutation(len(pts2))
+    ptsR, ownR = np.repeat(cR, 40, axis=0), np.repeat(np.arange(pairs), 40)
+    oR = rng.permutation(len(ptsR))
+    X0 = np.ascontiguousarray(np.concatenate([pts2[o2], ptsR[oR]]))
+    order = rng.permutation(pairs)
+    first = Params(1e-4, 2.5e-9, k_first, 0.5, 8.0, 0.1, 0.5, 0.25, 0.05, d)
+    meta = dict(kind="victims-set-params", tainted=True, first=(first, X0), pair=order, k_first=k_first,
+                built_R2=(np.arange(len(o2)), own2[o2]), built_R=(len(o2) + np.arange(len(oR)), ownR[oR]))
+    return None, None, first._replace(k=k), np.ascontiguousarray(X[order]), meta
+
+
+def stale(seed, m_p, m_o, d, n, k=4.0, filt=False, clean=False):
+    """General tables whose stored preference entries say nothing about their variances: k or 1 at random, in one row
+    in twelve a few entries between 1 and k, in another twelfth a few below both (not with `clean`: entries of k or 1
+    only - the handle stays untainted and takes the scans of the common case).  Rows in groups of about four (jitter 0.02
+    around centres in [0.1, 0.9)^d), pcore weights 4 .. 40, outlier weights 1 .. 3 with a third at beta mu - 1 = 3 exactly:
+    the first join promotes them AT w == beta mu.  filt: pi = d - 2, rows carry 0 .. 4 dimensions of variance 4 delta_sq.
+    Points: near pcore centroids, near outlier centroids (half of them near those of weight 3), near pcores that hold
+    exactly pi entries above 1, and anywhere in the box (new outliers)."""
+    rng = np.random.default_rng(seed)
+    pi = d - 2 if filt else d
+    delta_sq = 1e-5 if filt else 0.05 ** 2
+    beta, mu = 0.5, 8.0
+    lo, hi = min(1.0, k), max(1.0, k)
+
+    def rows(m, first_group):
+        g = first_group + np.arange(m) // 4
+        cen = rng.uniform(0.1, 0.9, (int(g.max()) + 1 if m else 0, d))[g - first_group] + rng.normal(0.0, 0.02, (m, d))
+        var = rng.uniform(0.0, 1e-6, (m, d))
+        pref = np.where(rng.random((m, d)) < rng.random((m, 1)), k, 1.0)
+        for r in range(m):
+            if filt:
+                var[r, rng.choice(d, int(rng.integers(0, 5)), replace=False)] = 4.0 * delta_sq
+            how = int(rng.integers(0, 12))
+            if not clean and how < 2:
+                at = rng.choice(d, min(d, 3), replace=False)
+                pref[r, at] = rng.uniform(lo, hi, len(at)) if how == 0 else 0.5 * lo
+        return cen, var, pref
+
+    cen, var, pref = rows(m_p, 0)
+    exact = np.zeros(m_p, bool)
+    exact[rng.random(m_p) < 0.1] = True                    # exactly pi stored entries above 1
+    for r in np.flatnonzero(exact):
+        pref[r] = 1.0
+        pref[r, rng.choice(d, pi, replace=False)] = k if k > 1.0 else 2.0
+    if clean:
+        exact &= k > 1.0
+        pref[(pref != 1.0) & (pref != k)] = k
+    pcores = _table(rng, cen, var, pref, rng.uniform(4.0, 40.0, m_p)) if m_p else None
+    cen_o, var_o, pref_o = rows(m_o, m_p // 4 + 1)
+    w_o = np.where(rng.random(m_o) < 0.33, beta * mu - 1.0, rng.uniform(1.0, 3.0, m_o))
+    outliers = _outlier_table(rng, cen_o, var_o, pref_o, w_o) if m_o else None
+    at_eq = np.flatnonzero(w_o == beta * mu - 1.0)
+    kinds = rng.choice(4, n, p=[0.4, 0.3, 0.15, 0.15])
+    X = rng.uniform(0.1, 0.9, (n, d))
+    for i in range(n):
+        src = None
+        if kinds[i] == 0 and m_p:
+            src = cen[rng.integers(0, m_p)]
+        elif kinds[i] == 1 and m_o:
+            src = cen_o[rng.choice(at_eq)] if len(at_eq) and rng.random() < 0.5 else cen_o[rng.integers(0, m_o)]
+        elif kinds[i] == 2 and exact.any():
+            src = cen[rng.choice(np.flatnonzero(exact))]
+        if src is not None:
+            X[i] = src + rng.normal(0.0, 0.003, d)
+    par = Params(0.05 ** 2, delta_sq, k, beta, mu, 0.1, 0.5, 0.25, 0.05, pi)
+    tainted = not clean
+    meta = dict(kind="stale", tainted=tainted, full=m_p >= 31 and m_o >= 31 and n >= 127,
+                eq_uids=outliers.uid[at_eq] if m_o else np.zeros(0, np.int64))
+    return pcores, outliers, par, np.ascontiguousarray(X), meta
+
+
+def lattice(seed, m_p, m_o, d, n):
+    """Centroids on a 1/8 grid, points on a 1/16 grid, weights 3 or 7 (w + 1 a power of two), variances 0, entries of k = 4 or
+    1, thresholds dyadic (eps_sq 3/256, delta_sq 1/16, beta mu 8): every sum is exact in any order, so equal distances ARE
+    equal.  Groups of about 24 rows around centres 8 apart in dimension 0, offsets of -2 .. 2 eighths in three dimensions
+    (rows of one group may coincide).  Planted on rows that stand alone (4 apart in dimension 1, no group near them):
+      copies   one row at pcore-list positions 0, 31, 32, 33 and the last (those the list has), another on the outlier list
+               alike; points on its centroid and 1/16 beside it: the first copy in list order takes them all;
+      equal    rows of weight 3 with every entry k and a point at c + 1/2 e_1: tentative variance 3/64 (<= delta_sq), radius
+               3/256 == eps_sq, accepted;
+      beyond   the same with the point at c + 9/16 e_1: radius 243/16384, rejected - a new outlier.
+    The other points: a row's centroid plus -2 .. 2 sixteenths in up to three dimensions (midway between two rows of a group:
+    an exact tie), and a few far from everything.  Outliers of weight 7 are promoted at w + 1 == beta mu."""
+    assert d >= 3
+    rng = np.random.default_rng(seed)
+    k, eps_sq, delta_sq, beta, mu = 4.0, 3.0 / 256.0, 1.0 / 16.0, 0.5, 16.0
+
+    def general(m, base):
+        g = np.arange(m) // 24
+        ng = int(g.max()) + 1 if m else 0
+        centre = np.zeros((ng, d))
+        centre[:, 0] = base + 8.0 * np.arange(ng)
+        centre += rng.integers(0, 8, (ng, d)) / 8.0
+        off = np.zeros((m, d))
+        for gi in range(ng):
+            r = np.flatnonzero(g == gi)
+            act = rng.choice(d, 3, replace=False)
+            off[np.ix_(r, act)] = rng.integers(-2, 3, (len(r), 3)) / 8.0
+        return centre[g] + off, np.where(rng.random((m, d)) < 0.5, k, 1.0), rng.choice([3.0, 7.0], m)
+
+    def alone(j, row):                                     # centroid of planted row j of list `row` (0 pcores, 1 outliers)
+        c = np.zeros(d)
+        c[0], c[1] = -16.0 - 8.0 * row, 4.0 * j
+        return c
+
+    def build(m, row, n_eq):
+        """A list of m rows: copies at 0, 31, 32, 33, m - 1, then n_eq `equal` and n_eq `beyond` rows at random other
+        positions, general rows elsewhere."""
+        copy_at = sorted({p for p in (0, 31, 32, 33, m - 1) if 0 <= p < m})
+        free = np.array([p for p in rng.permutation(m) if p not in copy_at], np.int64)
+        n_eq = min(n_eq, len(free) // 2)
+        eq_at, be_at = free[:n_eq], free[n_eq:2 * n_eq]
+        cen, pref, w = general(m, 0.0 if row == 0 else 4096.0)
+        for p in copy_at:
+            cen[p], pref[p], w[p] = alone(0, row), np.where(np.arange(d) % 2 == 0, k, 1.0), 3.0
+        for j, p in enumerate(np.concatenate([eq_at, be_at])):
+            cen[p], pref[p], w[p] = alone(1 + j, row), k, 3.0
+        return cen, pref, w, copy_at, eq_at, be_at
+
+    cen, pref, w, copy_p, eq_at, be_at = build(m_p, 0, 4)
+    pcores = _table(rng, cen, 0.0, pref, w) if m_p else None
+    cen_o, pref_o, w_o, copy_o, _, _ = build(m_o, 1, 0)
+    outliers = _outlier_table(rng, cen_o, 0.0, pref_o, w_o) if m_o else None
+    e1 = np.zeros(d)
+    e1[1] = 1.0                                            # (dimension 1: "e_1" counting from 0)
+    pts, tag = [], []
+
+    def add(x, t):
+        pts.append(x)
+        tag.append(t)
+
+    for c_at, cc, t in ((copy_p, cen, "copy_p"), (copy_o, cen_o, "copy_o")):
+        if c_at:
+            for x in (cc[0], cc[0], cc[0] + e1 / 16.0, cc[0] + e1 / 16.0, cc[0] + e1 / 16.0):
+                add(x, t)
+    for p in eq_at:
+        add(cen[p] + e1 / 2.0, "equal")
+    for p in be_at:
+        add(cen[p] + 9.0 * e1 / 16.0, "beyond")
+    both = np.concatenate([cen.reshape(-1, d), cen_o.reshape(-1, d)])
+    taken = set(copy_p) | set(int(p) for p in eq_at) | set(int(p) for p in be_at) | set(m_p + p for p in copy_o)
+    pool = np.array([r for r in range(len(both)) if r not in taken], np.int64)
+    while len(pts) < n:
+        if len(pool) == 0 or rng.random() < 0.05:
+            x = np.zeros(d)
+            x[0], x[2] = -4096.0 - 64.0 * len(pts), 1.0 / 16.0    # far from everything, and from one another
+            add(x, "far")
+        else:
+            x = both[rng.choice(pool)].copy()
+            at = rng.choice(d, int(rng.integers(0, 4)), replace=False)
+            x[at] += rng.integers(-2, 3, len(at)) / 16.0
+            add(x, "near")
+    pts, tag0 = np.array(pts), np.array(tag)
+    order = rng.permutation(len(pts))
+    X, tag = pts[order], tag0[order]
+    for t in ("copy_p", "copy_o"):                         # (these keep their order: a point beside the centroid moves it)
+        X[tag == t] = pts[tag0 == t]
+    par = Params(eps_sq, delta_sq, k, beta, mu, 0.1, 0.5, 0.25, 1.0 / 32.0, d)
+    meta = dict(kind="lattice", tainted=False, tag=tag, eq_at=eq_at, be_at=be_at,
+                first_copy=(int(pcores.uid[0]) if copy_p else None, int(outliers.uid[0]) if copy_o else None))
+    return pcores, outliers, par, np.ascontiguousarray(X), meta
+
+
+def lattice_present(pcores, par, X, meta):
+    """(points whose smallest distance to the injected pcores is shared by two or more rows, `equal` points whose tentative
+    radius == eps_sq, `beyond` points whose radius is above it) recomputed in numpy - dyadic terms, exact in any order."""
+    ties = 0
+    near = np.flatnonzero(meta["tag"] == "near")[:256]
+    for i in near:
+        dist = ((X[i] - pcores.cen) ** 2 / pcores.pref).sum(axis=1)
+        ties += int((dist == dist.min()).sum() > 1)
+    eq_pts, be_pts = X[meta["tag"] == "equal"], X[meta["tag"] == "beyond"]
+
+    def radius(pts, rows):                                 # of the planted row each point belongs to (same e_1 line)
+        out = []
+        for x in pts:
+            r = [p for p in rows if pcores.cen[p][0] == x[0] and pcores.cen[p][1] <= x[1] < pcores.cen[p][1] + 1.0]
+            out.append(tentative(pcores, np.array(r[:1]), x[None, :], par)[1][0])
+        return np.array(out)
+
+    return ties, int((radius(eq_pts, meta["eq_at"]) == par.eps_sq).sum()), int((radius(be_pts, meta["be_at"]) > par.eps_sq).sum())
+
+
+# ---- the two sides of an online case ------------------------------------------------------------------------------------
+
+def oracle_online(case):
+    """The oracle's side of a case: dict(o=the oracle afterwards, uid, path; first=(uid, path) and mid=the pcore list after
+    the first call where the case has one)."""
+    pcores, outliers, par, X, meta = case
+    res = {}
+    if "first" in meta:
+        par0, X0 = meta["first"]
+        o = make_oracle(par0)
+        o.online_microcluster_maintenance(X0, 0, reset_param=False, offline=False)
+        res["first"] = (o.labels_uid.copy(), o.paths.copy())
+        res["mid"] = o.table(0)
+        o.__dict__.update(epsilon_squared=par.eps_sq, delta_squared=par.delta_sq, k=par.k, beta=par.beta, mu=par.mu,
+                          omicron=par.omicron, upsilon=par.ups_eps, delta=par.delta, pi=par.pi)
+    else:
+        o = make_oracle(par, pcores, outliers)
+    o.online_microcluster_maintenance(X, 0, reset_param=False, offline=False)
+    res.update(o=o, uid=o.labels_uid.copy(), path=o.paths.copy())
+    return res
+
+
+def handle_online(h, case):
+    """The library's side on a handle that holds nothing: (uid, path) of the case's points, and of the first call's."""
+    pcores, outliers, par, X, meta = case
+    first = None
+    if "first" in meta:
+        par0, X0 = meta["first"]
+        h.set_params(*par0)
+        first = h.online(X0)
+        h.set_params(*par)
+    else:
+        fill_handle(h, par, pcores, outliers)
+    return h.online(X), first
+
+
+def same_online(h, labels, exp, what=""):
+    """Bit equality of uid and path per point (the first differing point is named), of both lists and of the id counters.
+    labels: what handle_online returned; exp: what oracle_online returned."""
+    (uid, path), first = labels
+    pairs = [("", uid, path, exp["uid"], exp["path"])]
+    if first is not None:
+        pairs.insert(0, ("first call: ", first[0], first[1]) + tuple(exp["first"]))
+    for pre, gu, gp, eu, ep in pairs:
+        for key, a, b in (("uid", gu, eu), ("path", gp, ep)):
+            diff = _first_diff(a, b)
+            assert diff is None, "%s %s%s per point (library / oracle): %s" % (what, pre, key, diff)
+    same_lists(h, exp["o"], what)
+
+
+def group_online(world, case, device=0, thresholds=(0, 0), tuning=None):
+    """The case on `world` handles of one in-process group, one host thread per rank; every split forced on from the first
+    row unless `thresholds` says otherwise (None: the library's defaults).  Returns the handles (the caller closes them),
+    their labels and their statistics by rank."""
+    def work(h, rank):
+        if thresholds is not None:
+            h.set_shard_thresholds(*thresholds)
+        if tuning:
+            h.set_tuning(**tuning)
+        return handle_online(h, case)
+
+    hs, labels = _run_group(world, work, device)
+    return hs, labels, [h.stats() for h in hs]
+
+
+def check_online(case, res):
+    """Asserts on the ORACLE's result that the case holds what it exists for (no GPU involved)."""
+    pcores, outliers, par, X, meta = case
+    uid, path, kind = res["uid"], res["path"], meta["kind"]
+    if kind == "victims":
+        t = meta["rows"]
+        want = 5 if meta["on_outliers"] else 0
+        assert (path == want).all(), "paths %r" % np.unique(path)
+        assert np.array_equal(uid, t.uid[meta["R"][meta["pair"]]]), "%d points not absorbed by their R" % int(
+            (uid != t.uid[meta["R"][meta["pair"]]]).sum())
+        if meta["filt"]:
+            r, r2, r3 = (meta[key][meta["pair"]] for key in ("R", "R2", "R3"))
+            assert (tentative(t, r3, X, par)[0] > par.pi).all()                     # rejected ...
+            assert (tentative(t, r, X, par)[0] <= par.pi).all() and (tentative(t, r2, X, par)[0] <= par.pi).all()
+            near = ((X - t.cen[r3]) ** 2 / t.pref[r3]).sum(axis=1)
+            assert (near < ((X - t.cen[r]) ** 2 / t.pref[r]).sum(axis=1)).all()      # ... though nearer than R
+    elif kind == "victims-set-params":
+        fu, fp = res["first"]
+        pairs = len(X)
+        uid_of = {}
+        for name in ("built_R", "built_R2"):
+            at, own = meta[name]
+            per = [np.unique(fu[at[own == p]]) for p in range(pairs)]
+            assert all(len(u) == 1 for u in per), "%s: a pair's points went to several rows" % name
+            uid_of[name] = np.array([u[0] for u in per])
+        mid = res["mid"]
+        row_of = {int(u): i for i, u in enumerate(mid["uid"])}
+        assert len(mid["uid"]) == 2 * pairs
+        for p in range(pairs):
+            a, b = row_of[int(uid_of["built_R"][p])], row_of[int(uid_of["built_R2"][p])]
+            assert (mid["pref"][a] == meta["k_first"]).all() and mid["w"][a] == 40.0
+            assert (mid["pref"][b] == 1.0).all() and mid["w"][b] == 10.0
+        assert (path == 0).all() and np.array_equal(uid, uid_of["built_R"][meta["pair"]])
+    elif kind == "stale":
+        if meta["full"]:
+            seen = set(int(x) for x in np.unique(path))
+            assert {0, 1, 5, 2} <= seen, "paths %r" % sorted(seen)
+            first_join = {}
+            for i in range(len(uid)):
+                first_join.setdefault(int(uid[i]), int(path[i]))
+            at_eq = [first_join[int(u)] for u in meta["eq_uids"] if int(u) in first_join]
+            assert 5 in at_eq, "no outlier of weight beta mu - 1 was promoted by its first join"
+    elif kind == "lattice":
+        tag = meta["tag"]
+        fp, fo = meta["first_copy"]
+        if fp is not None and (tag == "copy_p").any():
+            assert (uid[tag == "copy_p"] == fp).all() and (path[tag == "copy_p"] == 0).all()
+        if fo is not None and (tag == "copy_o").any():
+            assert (uid[tag == "copy_o"] == fo).all() and ((path[tag == "copy_o"] & 3) == 1).all()
+        if pcores is not None and len(pcores) >= 64 and len(X) >= 127:
+            ties, n_eq, n_be = lattice_present(pcores, par, X, meta)
+            assert ties > 0 and n_eq > 0 and n_be > 0, (ties, n_eq, n_be)
+            assert n_eq == int((tag == "equal").sum()) and n_be == int((tag == "beyond").sum())
+            assert (path[tag == "equal"] == 0).all() and sorted(uid[tag == "equal"]) == sorted(pcores.uid[meta["eq_at"]])
+            assert (path[tag == "beyond"] == 2).all() and (path[tag == "far"] == 2).all()
+            if outliers is not None and len(outliers) >= 64:
+                assert (path == 5).any()
+    else:
+        raise ValueError(kind)
+
+
+# every injected table of tests/test_online_tables.py: name -> (generator, arguments).  Row counts around the point tile and
+# wave (31 .. 33, 127 .. 129), one list empty, up to 4 096 rows; 1 to 2 048 points; every width at which the online phase
+# takes another kernel (3: k_seq_r; 5, 8: k_scan pads for itself; 13: padded rows; 14 .. 64: the ladder; 80, 200: k_seq_g and
+# its wide form).  The tables of 9 999 rows and more select forms by table size (see the tests that use them).
+ONLINE_TABLES = {
+    "victims-k4-16x14": (victims, dict(seed=101, pairs=16, d=14)),
+    "victims-k4-300x16": (victims, dict(seed=102, pairs=300, d=16)),
+    "victims-k4-600x20": (victims, dict(seed=103, pairs=600, d=20)),
+    "victims-k4-1000x32": (victims, dict(seed=104, pairs=1000, d=32)),
+    "victims-k4-2048x40": (victims, dict(seed=105, pairs=2048, d=40)),
+    "victims-k3-600x20": (victims, dict(seed=106, pairs=600, d=20, k=3.0)),
+    "victims-k0.5-600x20": (victims, dict(seed=107, pairs=600, d=20, k=0.5)),
+    "victims-k3-200x14": (victims, dict(seed=108, pairs=200, d=14, k=3.0, stored=768.0)),
+    "victims-outliers-600x20": (victims, dict(seed=109, pairs=600, d=20, on_outliers=True)),
+    "victims-outliers-k3-500x40": (victims, dict(seed=110, pairs=500, d=40, k=3.0, on_outliers=True)),
+    "victims-filter-600x20": (victims, dict(seed=111, pairs=600, d=20, filt=True)),
+    "victims-filter-k3-300x32": (victims, dict(seed=112, pairs=300, d=32, k=3.0, filt=True)),
+    "victims-k4-8x3": (victims, dict(seed=113, pairs=8, d=3)),
+    "victims-k4-12x5": (victims, dict(seed=114, pairs=12, d=5)),
+    "victims-k4-40x8": (victims, dict(seed=115, pairs=40, d=8)),
+    "victims-k4-64x13": (victims, dict(seed=116, pairs=64, d=13)),
+    "victims-k4-200x64": (victims, dict(seed=117, pairs=200, d=64)),
+    "victims-k4-100x80": (victims, dict(seed=118, pairs=100, d=80)),
+    "victims-k4-50x200": (victims, dict(seed=119, pairs=50, d=200)),
+    "victims-set-params-200x20": (victims_by_set_params, dict(seed=120, pairs=200, d=20)),
+    "victims-set-params-k3-100x14": (victims_by_set_params, dict(seed=121, pairs=100, d=14, k=3.0)),
+    "victims-k4-10000x20": (victims, dict(seed=122, pairs=10000, d=20, points=2048)),
+    "stale-1+0x3": (stale, dict(seed=201, m_p=1, m_o=0, d=3, n=1)),
+    "stale-31+33x5": (stale, dict(seed=202, m_p=31, m_o=33, d=5, n=127)),
+    "stale-32+0x8": (stale, dict(seed=203, m_p=32, m_o=0, d=8, n=128)),
+    "stale-0+129x13": (stale, dict(seed=204, m_p=0, m_o=129, d=13, n=129)),
+    "stale-127+128x14": (stale, dict(seed=205, m_p=127, m_o=128, d=14, n=500, filt=True)),
+    "stale-1000+500x16": (stale, dict(seed=206, m_p=1000, m_o=500, d=16, n=1000, k=3.0)),
+    "stale-3000+1096x20": (stale, dict(seed=207, m_p=3000, m_o=1096, d=20, n=2048)),
+    "stale-filter-2000+1000x20": (stale, dict(seed=208, m_p=2000, m_o=1000, d=20, n=2048, filt=True)),
+    "stale-k0.5-600x32": (stale, dict(seed=209, m_p=400, m_o=200, d=32, n=700, k=0.5)),
+    "stale-filter-1500x40": (stale, dict(seed=210, m_p=1000, m_o=500, d=40, n=1000, k=3.0, filt=True)),
+    "stale-600x64": (stale, dict(seed=211, m_p=400, m_o=200, d=64, n=600)),
+    "stale-300x80": (stale, dict(seed=212, m_p=200, m_o=100, d=80, n=300)),
+    "stale-filter-150x200": (stale, dict(seed=213, m_p=100, m_o=50, d=200, n=200, filt=True)),
+    "clean-2000+1000x20": (stale, dict(seed=214, m_p=2000, m_o=1000, d=20, n=2048, clean=True)),
+    "clean-filter-1000+500x14": (stale, dict(seed=215, m_p=1000, m_o=500, d=14, n=1000, clean=True, filt=True)),
+    "clean-9999x20": (stale, dict(seed=216, m_p=6999, m_o=3000, d=20, n=1024, clean=True)),
+    "clean-10000x20": (stale, dict(seed=216, m_p=7000, m_o=3000, d=20, n=1024, clean=True)),
+    "clean-10001x20": (stale, dict(seed=216, m_p=7001, m_o=3000, d=20, n=1024, clean=True)),
+    "clean-19999x20": (stale, dict(seed=217, m_p=14999, m_o=5000, d=20, n=1024, clean=True)),
+    "clean-20000x20": (stale, dict(seed=217, m_p=15000, m_o=5000, d=20, n=1024, clean=True)),
+    "lattice-33+33x3": (lattice, dict(seed=301, m_p=33, m_o=33, d=3, n=127)),
+    "lattice-64+40x5": (lattice, dict(seed=312, m_p=64, m_o=40, d=5, n=200)),
+    "lattice-128+127x8": (lattice, dict(seed=302, m_p=128, m_o=127, d=8, n=300)),
+    "lattice-129+64x13": (lattice, dict(seed=303, m_p=129, m_o=64, d=13, n=300)),
+    "lattice-1000+500x14": (lattice, dict(seed=304, m_p=1000, m_o=500, d=14, n=1000)),
+    "lattice-300+150x16": (lattice, dict(seed=310, m_p=300, m_o=150, d=16, n=400)),
+    "lattice-3000+1096x20": (lattice, dict(seed=305, m_p=3000, m_o=1096, d=20, n=2048)),
+    "lattice-500+250x32": (lattice, dict(seed=311, m_p=500, m_o=250, d=32, n=600)),
+    "lattice-1000+500x40": (lattice, dict(seed=306, m_p=1000, m_o=500, d=40, n=1000)),
+    "lattice-400+200x64": (lattice, dict(seed=307, m_p=400, m_o=200, d=64, n=500)),
+    "lattice-200+100x80": (lattice, dict(seed=308, m_p=200, m_o=100, d=80, n=300)),
+    "lattice-100+64x200": (lattice, dict(seed=313, m_p=100, m_o=64, d=200, n=200)),
+    "lattice-7000+3000x20": (lattice, dict(seed=309, m_p=7000, m_o=3000, d=20, n=1024)),
+}
+
+
+def build_online(name):
+    gen, kw = ONLINE_TABLES[name]
+    return gen(**kw)
+
+
 if __name__ == "__main__":  # the structure conditions of every table against the oracle alone (no GPU)
     import os
     import sys
     import time
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    for name in sys.argv[1:] or OFFLINE_TABLES:
+    unknown = [a for a in sys.argv[1:] if a not in ONLINE_TABLES and a not in OFFLINE_TABLES]
+    if unknown:
+        sys.exit("no such table: %s" % ", ".join(unknown))
+    for name in [a for a in sys.argv[1:] if a in ONLINE_TABLES] or ([] if sys.argv[1:] else ONLINE_TABLES):
+        t0 = time.time()
+        case = build_online(name)
+        t1 = time.time()
+        res = oracle_online(case)
+        check_online(case, res)
+        print("%-30s ok: %5d + %5d rows, %4d points, paths %s, build %.1f s, oracle %.1f s" % (
+            name, len(case[0]) if case[0] is not None else 0, len(case[1]) if case[1] is not None else 0, len(case[3]),
+            dict(zip(*[x.tolist() for x in np.unique(res["path"], return_counts=True)])), t1 - t0, time.time() - t1))
+    for name in [a for a in sys.argv[1:] if a in OFFLINE_TABLES] or ([] if sys.argv[1:] else OFFLINE_TABLES):
         t0 = time.time()
         t, par, meta = build_table(name)
         info, clusters = oracle_offline(make_oracle(par, t))
