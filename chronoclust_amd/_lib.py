@@ -48,7 +48,7 @@ class CcStats(C.Structure):
                 ("calib_allgather_us", C.c_double), ("calib_scan_ns_per_row_dim", C.c_double),
                 ("split_threshold_row_dims", C.c_int64), ("split_threshold_row_dims_pruned", C.c_int64),
                 ("missed_plain_launches", C.c_int64), ("seed16_launches", C.c_int64),
-                ("pad_rows_launches", C.c_int64)]
+                ("pad_rows_launches", C.c_int64), ("assign_points", C.c_int64), ("assign_launches", C.c_int64)]
 
 
 POLICY_MAX_ROUNDS = 8
@@ -128,6 +128,7 @@ SYMBOLS = {
     "cc_points_download": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "cc_labels_download": (C.c_int, [C.c_void_p, _i64p, _i8p]),
     "cc_online": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _i64p, _i8p]),
+    "cc_assign": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _i64p, _i8p, _dp]),
     "cc_count": (C.c_int, [C.c_void_p, C.c_int]),
     "cc_dim": (C.c_int, [C.c_void_p]),
     "cc_counters": (C.c_int, [C.c_void_p, _i64p, _i64p]),
@@ -473,6 +474,21 @@ class Handle(object):
         self.points_upload(x)
         self.online_run()
         return self.labels_download()
+
+    def assign(self, x, want_path=True, want_dist=False):
+        """cc_assign: per point of x [n, d] what the online phase would do with it if it were the very next point, against
+        the table as it stands - (uid, path, dist): the creation number of the microcluster it would join (-1: it would
+        create one), 0 pcore / 1 outlier / 5 outlier that the add promotes / 2 new, the projected distance to that
+        microcluster (-1.0 for path 2); path and dist are None unless wanted.  Nothing of the handle changes."""
+        x = _f64(x)
+        if x.ndim != 2:
+            raise ValueError("points must be a 2-d array")
+        n = x.shape[0]
+        uid = np.empty(n, dtype=np.int64)
+        path = np.empty(n, dtype=np.int8) if want_path else None
+        dist = np.empty(n, dtype=np.float64) if want_dist else None
+        self._check(self._lib.cc_assign(self._h, _ptr(x), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
+        return uid, path, dist
 
     def count(self, kind):
         return self._check(self._lib.cc_count(self._h, kind))

@@ -249,6 +249,44 @@ class HDDStream(object):
         # chronoclust_amd.multi.point_cluster_index is the same join in numpy (tests compare the two)
         return self._h.point_clusters().astype(np.int64)
 
+    # ---- read-only assignment (cc_assign) ----------------------------------------------------------
+
+    def _assign_params(self):
+        """The parameters assign() scores against: those of the last timepoint, which the handle holds.  A model that was
+        restored (set_state) and has not seen a timepoint since holds placeholders for the dataset-dependent ones: mu and
+        pi are derived from the restored dataset size and width as hddstream.py:89-128 does (omicron plays no part)."""
+        if self.mu is None and self.dataset_dimensionality > 0:
+            config_pi = float(self.config['pi'])
+            pi = self.dataset_dimensionality if config_pi <= 0 else round(config_pi)
+            self._h.set_params(self.epsilon_squared, self.delta_squared, self.k, self.beta,
+                               float(self.config['mu']) * self.dataset_size, 0.0, self.upsilon, self.upsilon ** 2,
+                               self.delta, int(pi))
+
+    def assign(self, input_dataset):
+        """Where would these events go?  For every row of `input_dataset` - values in the model's own space, the one
+        online_microcluster_maintenance takes - what the online phase would do with it if it were the very next point:
+        (uid, path) with uid the creation number of the microcluster it would join (-1: it would create one) and path 0
+        pcore / 1 outlier / 5 outlier that the add would promote / 2 new.  Every point is scored on its own against the
+        microclusters as they stand; nothing of the model changes (Handle.assign)."""
+        X = np.ascontiguousarray(np.asarray(input_dataset, dtype=np.float64))
+        if X.ndim != 2:
+            raise ValueError("input_dataset must be 2-d [N, d]")
+        self._assign_params()
+        uid, path, _ = self._h.assign(X)
+        return uid, path
+
+    def assign_clusters(self, input_dataset):
+        """For every row the index into final_clusters of the cluster that holds the pcore microcluster the point would
+        join, -1 for points that would join an outlier microcluster or create one and for pcore microclusters outside
+        every cluster.  Valid after offline_clustering; the join is multi.point_cluster_index."""
+        from ..multi import point_cluster_index
+        uid, path = self.assign(input_dataset)
+        if getattr(self, "_cl_arrays", None) is None:
+            return np.full(len(uid), -1, np.int64)
+        pc = self._tables.get(_lib.PCORE) or self._h.export(_lib.PCORE)  # (read, not cached: no view is touched)
+        mem, off = self._cl_arrays[0], self._cl_arrays[1]
+        return point_cluster_index(np.where(path == 0, uid, -1), pc["id"], pc["uid"], mem, off)
+
     def cluster_records(self):
         """The tracking-side records of this timepoint's clusters: what app.py:181-190 builds one by one -
         Cluster(list(id_set), centroid, weight rounded to one decimal place, preferred dimensions) plus the member

@@ -267,7 +267,19 @@ struct RelaxedState {
     cc_relaxed_stats rstats{};
 };
 
-struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, OfflineResults, AssocScratch, RelaxedState {
+// cc_assign: the chunk buffers of the read-only assignment, two sets (one per stream; cc_api_assign.inc) - the points of a
+// chunk row-major and dimension-major, the segments' partial bests, the chunk's results, k_check_finite's words
+struct AssignBuffers {
+    struct Set {
+        DevBuf<double> X, Xt, dist;
+        DevBuf<long long> uid;
+        DevBuf<int8_t> path;
+        DevBuf<Cand> part;
+        DevBuf<int> bad;
+    } asg[2];
+};
+
+struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, OfflineResults, AssocScratch, RelaxedState, AssignBuffers {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;  // lookahead scans

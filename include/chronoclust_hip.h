@@ -152,6 +152,9 @@ typedef struct cc_stats {
     int64_t missed_plain_launches; /* plain scans (k_scan_u over a point list) for the points a guessed-threshold scan missed */
     int64_t seed16_launches;       /* seeded pruned chains whose seeds came from the matrix cores (k_seed16) with the tight threshold */
     int64_t pad_rows_launches;     /* snapshot scans that ran over padded operands (k_pad_rows in front of them: 9 <= d <= 64, d no compiled width) */
+    /* the last cc_assign (the only fields it writes; cc_online_run clears them with the rest) */
+    int64_t assign_points;         /* points it was asked to assign */
+    int64_t assign_launches;       /* k_assign_scan launches: one per chunk of points */
 } cc_stats;
 
 /* HDDStream.__init__ (hddstream.py:30-67): one state object on GPU `device`. */
@@ -192,6 +195,22 @@ int cc_points_prefetch(cc_handle* h, const double* x, int64_t n, int32_t d, cons
 int cc_online_run(cc_handle* h);
 int cc_labels_download(cc_handle* h, int64_t* out_uid, int8_t* out_path);
 int cc_online(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path);
+
+/* Read-only assignment: for each of the n points of x [n, d] (host, row-major), independently of every other point, what
+ * the per-point loop above would do with it if it were the very next point - against the table exactly as it stands.
+ *   out_uid[r]  = creation number of the microcluster the point would join, -1 if it would create one (no creation
+ *                 number is consumed)
+ *   out_path[r] (optional) = 0 nearest admissible pcore microcluster (pdim filter and radius test of the enlarged row,
+ *                 hddstream.py:311-337), 1 nearest outlier microcluster (:371-386), |4 if that add would promote it
+ *                 (:416-419), 2 new
+ *   out_dist[r] (optional) = projected distance to the reported row (paths 0, 1, 5), -1.0 for path 2
+ * i.e. the (uid, path) cc_online of that one point returns on a copy of the table, except that path 2 reports -1.
+ * Nothing is modified: both lists, the id counters, the resident points and their labels, every other field of cc_stats.
+ * The points travel in chunks through buffers of the call's own.  On a handle of a group the rank's table is read and no
+ * collective is called.  Preconditions and errors as for cc_online: cc_set_params first; CC_ERR_BAD_ARG for d outside
+ * 1..CC_MAX_DIM or different from the table's while it holds rows; CC_ERR_NONFINITE for NaN / Inf (the outputs are then
+ * unspecified).  n = 0 succeeds; an empty table gives path 2 everywhere. */
+int cc_assign(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path, double* out_dist);
 
 /* HDDStream.pcore_MC / outlier_MC (hddstream.py:56-57) in list order.
  * Any output pointer may be NULL.  cf1/cf2/cen/pref are [count, d]. */
