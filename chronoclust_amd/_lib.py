@@ -107,6 +107,7 @@ class CcRelaxedStats(C.Structure):
 
 
 _dp = C.POINTER(C.c_double)
+_fp = C.POINTER(C.c_float)
 _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
 _i8p = C.POINTER(C.c_int8)
@@ -129,6 +130,14 @@ SYMBOLS = {
     "cc_labels_download": (C.c_int, [C.c_void_p, _i64p, _i8p]),
     "cc_online": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _i64p, _i8p]),
     "cc_assign": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _i64p, _i8p, _dp]),
+    "cc_points_upload_f32": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int32]),
+    "cc_points_upload_scaled_f32": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int32, _dp, _dp]),
+    "cc_points_prefetch_f32": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int32, _dp, _dp]),
+    "cc_col_minmax_f32": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int32, _dp, _dp]),
+    "cc_online_f32": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int32, _i64p, _i8p]),
+    "cc_assign_f32": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int32, _i64p, _i8p, _dp]),
+    "cc_points_download_xt": (C.c_int, [C.c_void_p, _dp]),
+    "cc_f32_points": (C.c_int, [C.c_void_p, _i64p]),
     "cc_count": (C.c_int, [C.c_void_p, C.c_int]),
     "cc_dim": (C.c_int, [C.c_void_p]),
     "cc_counters": (C.c_int, [C.c_void_p, _i64p, _i64p]),
@@ -214,6 +223,23 @@ def load_host_only(path):
 
 def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def is_f32_points(a):
+    """True for what the `_f32` entry points take as it is: a C-contiguous 2-d float32 ndarray."""
+    return isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 2 and a.flags["C_CONTIGUOUS"]
+
+
+def as_points(a):
+    """Points as the library takes them without another copy: a C-contiguous 2-d float32 ndarray is returned as it is (the
+    very object - the `_f32` entry points read it, the device widens it), everything else - other dtypes, Fortran order,
+    strided views, lists - as a C-contiguous float64 array (_f64), as ever."""
+    return a if is_f32_points(a) else _f64(a)
+
+
+def xt_rows(d):
+    """Rows of the resident points' dimension-major copy (cc_points_download_xt): the padded scan width for 9 <= d <= 64."""
+    return scan_width(d, False, False)[0] if 8 < d <= 64 else d
 
 
 def _ptr(a, typ=_dp):
@@ -407,46 +433,59 @@ class Handle(object):
         self._check(self._lib.cc_decay_downgrade(self._h, float(factor)))
 
     def points_upload(self, x):
-        x = _f64(x)
+        x = as_points(x)
         if x.ndim != 2:
             raise ValueError("points must be a 2-d array")
         try:
-            self._check(self._lib.cc_points_upload(self._h, _ptr(x), x.shape[0], x.shape[1]))
+            if x.dtype == np.float32:
+                self._check(self._lib.cc_points_upload_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1]))
+            else:
+                self._check(self._lib.cc_points_upload(self._h, _ptr(x), x.shape[0], x.shape[1]))
         finally:
             self._prefetched = None  # adopted or discarded by the library: the array is no longer pinned by us
         self._n = x.shape[0]
 
     def points_prefetch(self, x, scale=None, min_=None):
         """Starts the background upload of the NEXT timepoint's points (cc_points_prefetch).  `x` must be the very
-        array (C-contiguous float64) that is later passed to points_upload / points_upload_scaled / online; the
+        array (C-contiguous float64 or float32) that is later passed to points_upload / points_upload_scaled / online; the
         handle keeps a reference to it until then.  Contract: the array must not be written to between this call and
         that upload - the upload is recognised by pointer, shape and scaling, and the copy already on the device is
         used as it is."""
-        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags["C_CONTIGUOUS"] and x.ndim == 2):
-            raise ValueError("points_prefetch needs a C-contiguous float64 [n, d] array (it is not copied)")
+        if not (isinstance(x, np.ndarray) and x.dtype in (np.float64, np.float32) and x.flags["C_CONTIGUOUS"] and x.ndim == 2):
+            raise ValueError("points_prefetch needs a C-contiguous float64 or float32 [n, d] array (it is not copied)")
         if x.shape[0] == 0:
             return
         scale = None if scale is None else _f64(scale)
         min_ = None if min_ is None else _f64(min_)
         self._prefetched = (x, scale, min_)  # keeps the buffers alive while the worker reads them
-        self._check(self._lib.cc_points_prefetch(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(scale), _ptr(min_)))
+        if x.dtype == np.float32:
+            self._check(self._lib.cc_points_prefetch_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(scale), _ptr(min_)))
+        else:
+            self._check(self._lib.cc_points_prefetch(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(scale), _ptr(min_)))
 
     def col_minmax(self, x):
         """Per-column (min, max) of x, NaN ignored, reduced on the device."""
-        x = _f64(x)
+        x = as_points(x)
         mn = np.empty(x.shape[1], dtype=np.float64)
         mx = np.empty(x.shape[1], dtype=np.float64)
-        self._check(self._lib.cc_col_minmax(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(mn), _ptr(mx)))
+        if x.dtype == np.float32:
+            self._check(self._lib.cc_col_minmax_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(mn), _ptr(mx)))
+        else:
+            self._check(self._lib.cc_col_minmax(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(mn), _ptr(mx)))
         return mn, mx
 
     def points_upload_scaled(self, x, scale, min_):
         """points_upload of x * scale + min_ (MinMaxScaler.transform), scaled on the device."""
-        x, scale, min_ = _f64(x), _f64(scale), _f64(min_)
+        x, scale, min_ = as_points(x), _f64(scale), _f64(min_)
         if x.ndim != 2 or scale.shape != (x.shape[1],) or min_.shape != (x.shape[1],):
             raise ValueError("points must be [n, d], scale and min_ [d]")
         try:
-            self._check(self._lib.cc_points_upload_scaled(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(scale),
-                                                          _ptr(min_)))
+            if x.dtype == np.float32:
+                self._check(self._lib.cc_points_upload_scaled_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(scale),
+                                                                  _ptr(min_)))
+            else:
+                self._check(self._lib.cc_points_upload_scaled(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(scale),
+                                                              _ptr(min_)))
         finally:
             self._prefetched = None
         self._n = x.shape[0]
@@ -459,6 +498,12 @@ class Handle(object):
         else:
             scale, min_ = _f64(scale), _f64(min_)
             self._check(self._lib.cc_points_download(self._h, _ptr(out), _ptr(scale), _ptr(min_)))
+        return out
+
+    def points_download_xt(self, d):
+        """The resident points' dimension-major copy as the scans read it: [xt_rows(d), n], the padded rows +0.0."""
+        out = np.empty((xt_rows(d), self._n), dtype=np.float64)
+        self._check(self._lib.cc_points_download_xt(self._h, _ptr(out)))
         return out
 
     def online_run(self):
@@ -480,14 +525,17 @@ class Handle(object):
         the table as it stands - (uid, path, dist): the creation number of the microcluster it would join (-1: it would
         create one), 0 pcore / 1 outlier / 5 outlier that the add promotes / 2 new, the projected distance to that
         microcluster (-1.0 for path 2); path and dist are None unless wanted.  Nothing of the handle changes."""
-        x = _f64(x)
+        x = as_points(x)
         if x.ndim != 2:
             raise ValueError("points must be a 2-d array")
         n = x.shape[0]
         uid = np.empty(n, dtype=np.int64)
         path = np.empty(n, dtype=np.int8) if want_path else None
         dist = np.empty(n, dtype=np.float64) if want_dist else None
-        self._check(self._lib.cc_assign(self._h, _ptr(x), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
+        if x.dtype == np.float32:
+            self._check(self._lib.cc_assign_f32(self._h, _ptr(x, _fp), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
+        else:
+            self._check(self._lib.cc_assign(self._h, _ptr(x), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
         return uid, path, dist
 
     def count(self, kind):
@@ -620,4 +668,13 @@ class Handle(object):
     def stats(self):
         s = CcStats()
         self._check(self._lib.cc_get_stats(self._h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in CcStats._fields_ if k != "reserved"}
+        out = {k: getattr(s, k) for k, _ in CcStats._fields_ if k != "reserved"}
+        out["f32_points"] = self.f32_points()
+        return out
+
+    def f32_points(self):
+        """Points this handle has taken in single precision since it was created (cc_f32_points): uploads, adopted
+        prefetches and assigns of float32 arrays.  stats() carries it as "f32_points" beside the fields of cc_stats."""
+        n = C.c_int64()
+        self._check(self._lib.cc_f32_points(self._h, C.byref(n)))
+        return n.value

@@ -580,6 +580,15 @@ int cc_online(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_
     return cc_labels_download(h, out_uid, out_path);
 }
 
+int cc_online_f32(cc_handle* h, const float* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path)
+{
+    int rc = cc_points_upload_f32(h, x, n, d);
+    if (rc != CC_OK) return rc;
+    rc = cc_online_run(h);
+    if (rc != CC_OK) return rc;
+    return cc_labels_download(h, out_uid, out_path);
+}
+
 int cc_count(cc_handle* h, int kind)
 {
     if (!h) return CC_ERR_BAD_ARG;
@@ -718,6 +727,13 @@ int cc_sync(cc_handle* h)
 }
 
 #include "cc_host_abi.inc"
+
+int cc_f32_points(cc_handle* h, int64_t* out)
+{
+    if (!h || !out) return CC_ERR_BAD_ARG;
+    *out = h->f32_points;
+    return CC_OK;
+}
 
 int cc_get_stats(cc_handle* h, cc_stats* out)
 {

@@ -3,12 +3,14 @@
 // first stream and odd ones on the second, so that a chunk's upload runs beside the previous chunk's scan.  Nothing of the
 // handle's state is written: not the table, the control block, the resident points or their labels, the window buffers, the
 // scan copies or the policy's carried state; of cc_stats only assign_points and assign_launches.  No collective is called:
-// on a handle of a group the rank's own table is read.  (included by cc_api.hip, the one translation unit, behind cc_handle.h)
+// on a handle of a group the rank's own table is read.  cc_assign_f32: the same chunks, each uploaded in single precision into
+// the set's raw buffer and taken in by k_ingest_f32 (cc_points.h) instead of the check and the transpose.  (included by
+// cc_api.hip, the one translation unit, behind cc_handle.h)
 
 namespace {
 
 // points per chunk: CHRONOCLUST_HIP_ASSIGN_CHUNK, else 32 MiB of coordinates (at most 262 144 points: a few thousand
-// workgroups per launch), whole point tiles
+// workgroups per launch), whole point tiles - in 8-byte terms also for single-precision points: both routes take the same chunks
 int64_t assign_chunk_points(const cc_handle* h, int d)
 {
     if (h->assign_chunk > 0) return h->assign_chunk;
@@ -27,9 +29,10 @@ int assign_segments(const cc_handle* h, int64_t chunk, int m_rows)
     return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, most), 64));
 }
 
-int assign_run(cc_handle* h, const double* x, int64_t n, int d, int64_t* out_uid, int8_t* out_path, double* out_dist,
+int assign_run(cc_handle* h, const void* x, bool f32, int64_t n, int d, int64_t* out_uid, int8_t* out_path, double* out_dist,
                bool* nonfinite)
 {
+    if (f32) h->f32_points += n;
     h->stats.assign_points = n;
     h->stats.assign_launches = 0;
     if (n == 0) return (int)CC_OK;
@@ -48,6 +51,7 @@ int assign_run(cc_handle* h, const double* x, int64_t n, int d, int64_t* out_uid
     for (int q = 0; q < sets; ++q) {
         AssignBuffers::Set& b = h->asg[q];
         b.X.ensure((size_t)chunk * d); b.Xt.ensure((size_t)chunk * d);
+        if (f32) b.raw.ensure((size_t)chunk * d);
         b.uid.ensure((size_t)chunk); b.path.ensure((size_t)chunk); b.dist.ensure((size_t)chunk);
         b.part.ensure((size_t)chunk * S * 2);
         b.bad.ensure(4);
@@ -60,11 +64,16 @@ int assign_run(cc_handle* h, const double* x, int64_t n, int d, int64_t* out_uid
         if (ci >= 2) sync_stream(h, st[q]);  // (the set's previous chunk has left its buffers)
         AssignBuffers::Set& b = h->asg[q];
         const long long tot = (long long)cn * d;
-        HIPCHK(hipMemcpyAsync(b.X.p, x + (size_t)off * d, (size_t)tot * 8, hipMemcpyHostToDevice, st[q]));
-        hipLaunchKernelGGL(k_check_finite, dim3((unsigned)std::min<long long>((tot + 255) / 256, 4096)), dim3(256), 0, st[q],
-                           (const double*)b.X.p, tot, b.bad.p);
-        hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st[q], (const double*)b.X.p,
-                           b.Xt.p, (long long)cn, d);
+        if (f32) {
+            HIPCHK(hipMemcpyAsync(b.raw.p, static_cast<const float*>(x) + (size_t)off * d, (size_t)tot * 4, hipMemcpyHostToDevice, st[q]));
+            ingest_launch(st[q], b.raw.p, cn, 0, cn, d, (size_t)d, b.X.p, b.Xt.p, nullptr, nullptr, b.bad.p);
+        } else {
+            HIPCHK(hipMemcpyAsync(b.X.p, static_cast<const double*>(x) + (size_t)off * d, (size_t)tot * 8, hipMemcpyHostToDevice, st[q]));
+            hipLaunchKernelGGL(k_check_finite, dim3((unsigned)std::min<long long>((tot + 255) / 256, 4096)), dim3(256), 0, st[q],
+                               (const double*)b.X.p, tot, b.bad.p);
+            hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st[q], (const double*)b.X.p,
+                               b.Xt.p, (long long)cn, d);
+        }
         const dim3 grid((unsigned)((cn + 63) / 64), (unsigned)S), block(64 * CC_ASSIGN_NW);
         with_bools([&](auto F, auto P) {
             hipLaunchKernelGGL((k_assign_scan<decltype(F)::value, decltype(P)::value>), grid, block, 0, st[q], rows, par,
@@ -89,18 +98,29 @@ int assign_run(cc_handle* h, const double* x, int64_t n, int d, int64_t* out_uid
     return (int)CC_OK;
 }
 
-}  // namespace
-
-extern "C" int cc_assign(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
-                         double* out_dist)
+int assign_points(cc_handle* h, const void* x, bool f32, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path, double* out_dist)
 {
     if (!h || n < 0 || (n > 0 && (!x || !out_uid))) return CC_ERR_BAD_ARG;
     if (!h->have_par) return fail(h, CC_ERR_BAD_ARG, "cc_set_params has not been called");
     if (d <= 0 || d > CC_MAX_DIM) return fail(h, CC_ERR_BAD_ARG, "d must be in 1.." + std::to_string(CC_MAX_DIM));
     if (h->hc.m_rows > 0 && d != h->d) return fail(h, CC_ERR_BAD_ARG, "dimensionality differs from the microclusters already held");
     bool nonfinite = false;
-    const int rc = guarded(h, [&]() { return assign_run(h, x, n, d, out_uid, out_path, out_dist, &nonfinite); });
+    const int rc = guarded(h, [&]() { return assign_run(h, x, f32, n, d, out_uid, out_path, out_dist, &nonfinite); });
     // (outside guarded: a refused query is no reason to give up the handle's group)
     if (rc == CC_OK && nonfinite) return fail(h, CC_ERR_NONFINITE, "input points contain NaN or Inf");
     return rc;
+}
+
+}  // namespace
+
+extern "C" int cc_assign(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
+                         double* out_dist)
+{
+    return assign_points(h, x, false, n, d, out_uid, out_path, out_dist);
+}
+
+extern "C" int cc_assign_f32(cc_handle* h, const float* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
+                             double* out_dist)
+{
+    return assign_points(h, x, true, n, d, out_uid, out_path, out_dist);
 }

@@ -268,10 +268,12 @@ struct RelaxedState {
 };
 
 // cc_assign: the chunk buffers of the read-only assignment, two sets (one per stream; cc_api_assign.inc) - the points of a
-// chunk row-major and dimension-major, the segments' partial bests, the chunk's results, k_check_finite's words
+// chunk row-major and dimension-major, the segments' partial bests, the chunk's results, k_check_finite's words; raw: the
+// chunk as it arrives in single precision (cc_assign_f32: k_ingest_f32 fills X and Xt from it)
 struct AssignBuffers {
     struct Set {
         DevBuf<double> X, Xt, dist;
+        DevBuf<float> raw;
         DevBuf<long long> uid;
         DevBuf<int8_t> path;
         DevBuf<Cand> part;
@@ -317,15 +319,20 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
     DevBuf<int8_t> lab_path;
     DevBuf<int> badflag;
     DevBuf<double> scr, scr2;  // scaler scratch
+    DevBuf<float> ingest_raw[2];  // cc_points_upload_f32: the two slabs of raw single-precision points (k_ingest_f32 reads them)
+    long long f32_points = 0;     // cc_f32_points: points taken in single precision since cc_create
 
     // cc_points_prefetch: the next timepoint's points, uploaded by a worker thread through page-locked staging
     struct Prefetch {
         std::thread worker;
         bool active = false;            // a worker was started and has not been adopted / discarded yet
-        const double* x = nullptr;      // what it uploads: pointer, shape, scaling (compared by the adopting upload)
+        const void* x = nullptr;        // what it uploads: pointer, shape, scaling, element type (compared by the adopting upload)
         long long n = 0;
         int d = 0;
         bool scaled = false;
+        bool f32 = false;               // x is float, staged piece by piece into raw[] and taken in by k_ingest_f32
+        long long piece = 0;            // ... points per piece: whole 64-point tiles that fit a page-locked buffer
+        DevBuf<float> raw[2];
         std::vector<double> scale, mn;
         DevBuf<double> X, Xt, sm;       // destination buffers (swapped with the handle's on adoption), scale / min
         DevBuf<int> bad;

@@ -54,6 +54,7 @@ struct Knobs {
     bool allow_seq_g = true;    // CHRONOCLUST_HIP_SEQG=0: no sequential kernel beyond the LDS image (k_seq_g, the table in HBM)
     int allow_sparse = 128;     // CHRONOCLUST_HIP_SPARSE=0: no sparse dirty scans (the tiles' scans or none); N: while at most one point in N needs them
     int assign_chunk = 0;       // CHRONOCLUST_HIP_ASSIGN_CHUNK=<points>: points per chunk of cc_assign (0, the default: 32 MiB of coordinates, at most 262 144 points)
+    int ingest_slab = 0;        // CHRONOCLUST_HIP_INGEST_SLAB=<points>: points per slab of raw float32 on its way through device staging, whole 64-point tiles (0, the default: 32 MiB of it - 16 MiB in a prefetch, a page-locked buffer's worth; the knob only ever shortens a slab)
     int assign_segments = 0;    // CHRONOCLUST_HIP_ASSIGN_SEGMENTS=1 .. 64: row segments per point tile of k_assign_scan (0, the default: by chunk and table size)
 };
 
@@ -104,6 +105,7 @@ void read_knobs(Knobs& k)
     knob_int_in(k.prune_rounds4, "CHRONOCLUST_HIP_PRUNE_WGS", 1, 64);
     knob_int_in(k.allow_sparse, "CHRONOCLUST_HIP_SPARSE", 0, INT_MAX);
     knob_int_in(k.assign_chunk, "CHRONOCLUST_HIP_ASSIGN_CHUNK", 1, 1 << 24);
+    knob_int_in(k.ingest_slab, "CHRONOCLUST_HIP_INGEST_SLAB", 1, 1 << 26);
     knob_int_in(k.assign_segments, "CHRONOCLUST_HIP_ASSIGN_SEGMENTS", 1, 64);
     knob_int_in(k.force_prune_rows, "CHRONOCLUST_HIP_FORCE_PRUNE_ROWS", INT_MIN, INT_MAX);  // (any integer, as atoi reads it)
     knob_int_in(k.p3_listed_rows, "CHRONOCLUST_HIP_P3_LISTED", INT_MIN, INT_MAX);

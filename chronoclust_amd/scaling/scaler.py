@@ -11,9 +11,11 @@ import pandas as pd
 
 def read_timepoint(filename):
     """One timepoint as float64 [N, d].  CSV with a header row as in the reference (app.py:170, scaler.py:31);
-    `.npy` files (binary side input: no text parse) are taken as they are."""
+    `.npy` files (binary side input: no text parse) are taken as they are - a float32 file stays float32 (cytometry events are
+    single precision at the source; the device widens them), anything else becomes float64."""
     if str(filename).endswith(".npy"):
-        return np.ascontiguousarray(np.load(filename), dtype=np.float64)
+        X = np.load(filename)
+        return np.ascontiguousarray(X, dtype=np.float32 if X.dtype == np.float32 else np.float64)
     return pd.read_csv(filename, header=0, sep=',').to_numpy()
 
 
@@ -29,7 +31,9 @@ class Scaler(object):
         if data_files is not None and handle is not None:
             lo = hi = None
             for filename in data_files:
-                X = np.ascontiguousarray(read_timepoint(filename), dtype=np.float64)
+                X = read_timepoint(filename)
+                if X.dtype != np.float32:
+                    X = np.ascontiguousarray(X, dtype=np.float64)
                 self.parsed[filename] = X
                 if X.shape[0] == 0:
                     continue

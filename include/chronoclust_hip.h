@@ -11,7 +11,8 @@
  * Conventions
  *  - plain C: pointers + sizes, no C++/torch types; every function returns 0
  *    on success or a negative cc_status; cc_last_error() has the text;
- *  - host pointers unless the name says "device"; row-major float64 [N, d];
+ *  - host pointers unless the name says "device"; row-major float64 [N, d]
+ *    (the `_f32` entry points: row-major float32 [N, d], widened on the device);
  *  - one handle = one HDDStream state on one GPU; a handle is not thread-safe;
  *  - all floating-point work is IEEE double, no FMA contraction, sums over
  *    dimensions strictly left to right, so results are bit-identical to the
@@ -211,6 +212,30 @@ int cc_online(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_
  * 1..CC_MAX_DIM or different from the table's while it holds rows; CC_ERR_NONFINITE for NaN / Inf (the outputs are then
  * unspecified).  n = 0 succeeds; an empty table gives path 2 everywhere. */
 int cc_assign(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path, double* out_dist);
+
+/* Single-precision points.  Cytometry events are 32-bit floats at the source (FCS files); each entry point below has the
+ * contract of its float64 sibling - arguments, errors, what happens to a group - with x row-major float32 [N, d].  The
+ * points cross the bus as they are, in slabs of whole 64-point tiles through two device staging buffers (at most 32 MiB
+ * each; CHRONOCLUST_HIP_INGEST_SLAB=<points> shortens them), and one kernel per slab (k_ingest_f32) widens them - float to
+ * double is exact -, applies scale_ / min_ in double (two roundings, as the float64 route), checks the stored values for
+ * NaN / Inf and writes the row-major and the dimension-major copy.  What the device then holds is bit for bit what the
+ * float64 entry point holds after the same values widened on the host, so every result is the same; scale, min_ and all
+ * outputs stay double.  A prefetch is adopted by the upload of the same pointer, shape, scaling AND element type.
+ * cc_assign_f32 takes the chunks cc_assign takes (cc_stats.assign_launches is the same).
+ * cc_f32_points: *out = the points taken in single precision since cc_create - uploads (an adopted cc_points_prefetch_f32
+ * included), cc_online_f32 and cc_assign_f32; no call clears it.  (A counter of its own, not a field of cc_stats: that
+ * structure's layout and size stay what callers were compiled against.) */
+int cc_points_upload_f32(cc_handle* h, const float* x, int64_t n, int32_t d);
+int cc_points_upload_scaled_f32(cc_handle* h, const float* x, int64_t n, int32_t d, const double* scale,
+                                const double* min_);
+int cc_points_prefetch_f32(cc_handle* h, const float* x, int64_t n, int32_t d, const double* scale, const double* min_);
+int cc_col_minmax_f32(cc_handle* h, const float* x, int64_t n, int32_t d, double* out_min, double* out_max);
+int cc_online_f32(cc_handle* h, const float* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path);
+int cc_assign_f32(cc_handle* h, const float* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path, double* out_dist);
+/* The resident points' dimension-major copy as the snapshot scans read it, whichever route brought them: out [rows, n] with
+ * rows = the padded scan width (cc_scan_width) for 9 <= d <= CC_WINDOW_MAX_DIM, else d; the rows beyond d hold +0.0. */
+int cc_points_download_xt(cc_handle* h, double* out);
+int cc_f32_points(cc_handle* h, int64_t* out);
 
 /* HDDStream.pcore_MC / outlier_MC (hddstream.py:56-57) in list order.
  * Any output pointer may be NULL.  cf1/cf2/cen/pref are [count, d]. */

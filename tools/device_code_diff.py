@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two builds of the library, kernel by kernel.
 
-    python tools/device_code_diff.py A/libchronoclust_hip.so B/libchronoclust_hip.so
+    python tools/device_code_diff.py A/libchronoclust_hip.so B/libchronoclust_hip.so [--renamed A_SYMBOL=B_SYMBOL ...]
 
 A change that only moves host code must leave every kernel as it was.  For each library the gfx950 code object is taken
 out of the .hip_fatbin section, disassembled, and cut into symbols; the per-kernel metadata (registers, LDS, scratch,
@@ -10,7 +10,9 @@ normalised: the __hip_cuid_* symbol (derived from the source path: ignored), add
 change the order of template instantiation and so the layout: the "// address: encoding" comments are dropped and the
 comparison is per symbol, without the padding (s_nop, zeros) behind a kernel's last instruction - the last kernel of the section is
 padded to its end, and which kernel that is follows the order), and the 32-bit literals of the s_add_u32 / s_addc_u32 pair
-behind an s_getpc_b64 (the PC-relative address of a global).  Prints the counts and every symbol that differs; exit status 1 on a difference."""
+behind an s_getpc_b64 (the PC-relative address of a global).  --renamed: a kernel of A that B holds under another symbol (a template that gained a parameter changes the mangled name
+of its instances): A's symbol takes B's name before the comparison.  Prints the counts and every symbol that differs; exit
+status 1 on a difference."""
 import os
 import re
 import subprocess
@@ -74,13 +76,24 @@ def function_symbols(co):
 
 
 def main():
-    if len(sys.argv) != 3:
+    args, renamed = sys.argv[1:], {}
+    while "--renamed" in args:
+        i = args.index("--renamed")
+        old, new = args[i + 1].split("=")
+        renamed[old] = new
+        del args[i:i + 2]
+    if len(args) != 2:
         sys.exit(__doc__)
     differ = 0
     with tempfile.TemporaryDirectory() as tmp:
-        cos = [code_object(lib, tmp, tag) for lib, tag in zip(sys.argv[1:], "ab")]
+        cos = [code_object(lib, tmp, tag) for lib, tag in zip(args, "ab")]
         for what, read in (("instructions", kernels_text), ("metadata", kernels_meta)):
             a, b = read(cos[0]), read(cos[1])
+            for old, new in sorted(renamed.items()):
+                for suffix in ("", ".kd"):
+                    if old + suffix in a:
+                        a[new + suffix] = a.pop(old + suffix).replace(old, new)
+                        print("  %s: A's %s compared as %s" % (what, old + suffix, new + suffix))
             print("%s: %d kernel symbols in A, %d in B" % (what, len(a), len(b)))
             for name in sorted(set(a) ^ set(b)):
                 print("  only in %s: %s" % ("A" if name in a else "B", name))
