@@ -101,6 +101,19 @@ class CcBatchGeometry(C.Structure):
                                          "pad")]
 
 
+class CcPointsView(C.Structure):
+    """cc_points_view: points where they lie; strides in elements."""
+    _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("d", C.c_int32), ("dtype", C.c_int32),
+                ("row_stride", C.c_int64), ("col_stride", C.c_int64)]
+
+
+# CC_DT_*: the element types a view may have, by numpy dtype (native byte order)
+DT_F64, DT_F32, DT_F16, DT_I8, DT_U8, DT_I16, DT_U16, DT_I32, DT_U32 = range(9)
+VIEW_DTYPES = {np.dtype(t): code for t, code in (
+    (np.float64, DT_F64), (np.float32, DT_F32), (np.float16, DT_F16), (np.int8, DT_I8), (np.uint8, DT_U8),
+    (np.int16, DT_I16), (np.uint16, DT_U16), (np.int32, DT_I32), (np.uint32, DT_U32))}
+
+
 class CcRelaxedStats(C.Structure):
     _fields_ = [("super_steps", C.c_int64), ("minibatch_points", C.c_int64), ("deferred_points", C.c_int64),
                 ("reserved", C.c_int64 * 5)]
@@ -111,6 +124,7 @@ _fp = C.POINTER(C.c_float)
 _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
 _i8p = C.POINTER(C.c_int8)
+_vp = C.POINTER(CcPointsView)
 
 # name -> (restype, argtypes): every symbol include/chronoclust_hip.h declares
 SYMBOLS = {
@@ -138,6 +152,12 @@ SYMBOLS = {
     "cc_assign_f32": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int32, _i64p, _i8p, _dp]),
     "cc_points_download_xt": (C.c_int, [C.c_void_p, _dp]),
     "cc_f32_points": (C.c_int, [C.c_void_p, _i64p]),
+    "cc_points_upload_view": (C.c_int, [C.c_void_p, _vp, _dp, _dp]),
+    "cc_points_prefetch_view": (C.c_int, [C.c_void_p, _vp, _dp, _dp]),
+    "cc_col_minmax_view": (C.c_int, [C.c_void_p, _vp, _dp, _dp]),
+    "cc_online_view": (C.c_int, [C.c_void_p, _vp, _i64p, _i8p]),
+    "cc_assign_view": (C.c_int, [C.c_void_p, _vp, _i64p, _i8p, _dp]),
+    "cc_view_points": (C.c_int, [C.c_void_p, _i64p]),
     "cc_count": (C.c_int, [C.c_void_p, C.c_int]),
     "cc_dim": (C.c_int, [C.c_void_p]),
     "cc_counters": (C.c_int, [C.c_void_p, _i64p, _i64p]),
@@ -235,6 +255,46 @@ def as_points(a):
     very object - the `_f32` entry points read it, the device widens it), everything else - other dtypes, Fortran order,
     strided views, lists - as a C-contiguous float64 array (_f64), as ever."""
     return a if is_f32_points(a) else _f64(a)
+
+
+def points_view(a):
+    """The cc_points_view of a 2-d ndarray the `_view` entry points take as it lies, else None.  Taken: the nine element
+    types of VIEW_DTYPES in native byte order, at least one point, and one of two layouts - rows form (columns one element
+    apart, rows at least d apart: C order, a range of columns of a C-order array) or columns form (rows one element apart,
+    columns at least n apart: Fortran order, a range of rows of a Fortran-order array, a transpose).  The stride of an axis
+    of length 1 says nothing and is set to what the rows form wants."""
+    if not isinstance(a, np.ndarray) or a.ndim != 2 or a.shape[0] == 0 or a.shape[1] == 0:
+        return None
+    code = VIEW_DTYPES.get(a.dtype) if a.dtype.isnative else None
+    if code is None:
+        return None
+    n, d = a.shape
+    size = a.dtype.itemsize
+    if a.strides[0] % size or a.strides[1] % size:
+        return None
+    rs, cs = a.strides[0] // size, a.strides[1] // size
+    if d == 1:
+        cs = 1
+    if n == 1:
+        rs = d if cs == 1 else 1
+    if not ((cs == 1 and rs >= d) or (rs == 1 and cs >= n)):
+        return None
+    return CcPointsView(a.ctypes.data, n, d, code, rs, cs)
+
+
+def points_source(a):
+    """(points, view): what the library takes of `a` with the fewest copies.  A C-contiguous 2-d float32 or float64 ndarray:
+    (a, None) - the very object, for the entry points it has always taken.  An array points_view accepts: (a, its
+    cc_points_view) - the very object again, read where it lies by the `_view` entry points.  Everything else - negative or
+    zero strides, both strides beyond one element, int64 / uint64 / bool / object, another byte order, lists, no points -
+    (as_points(a), None): a C-contiguous float64 copy."""
+    if isinstance(a, np.ndarray) and a.ndim == 2 and a.flags["C_CONTIGUOUS"] and a.dtype in (np.float32, np.float64) \
+            and a.dtype.isnative:
+        return a, None
+    view = points_view(a)
+    if view is not None:
+        return a, view
+    return as_points(a), None
 
 
 def xt_rows(d):
@@ -433,11 +493,13 @@ class Handle(object):
         self._check(self._lib.cc_decay_downgrade(self._h, float(factor)))
 
     def points_upload(self, x):
-        x = as_points(x)
+        x, view = points_source(x)
         if x.ndim != 2:
             raise ValueError("points must be a 2-d array")
         try:
-            if x.dtype == np.float32:
+            if view is not None:
+                self._check(self._lib.cc_points_upload_view(self._h, C.byref(view), None, None))
+            elif x.dtype == np.float32:
                 self._check(self._lib.cc_points_upload_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1]))
             else:
                 self._check(self._lib.cc_points_upload(self._h, _ptr(x), x.shape[0], x.shape[1]))
@@ -447,28 +509,34 @@ class Handle(object):
 
     def points_prefetch(self, x, scale=None, min_=None):
         """Starts the background upload of the NEXT timepoint's points (cc_points_prefetch).  `x` must be the very
-        array (C-contiguous float64 or float32) that is later passed to points_upload / points_upload_scaled / online; the
-        handle keeps a reference to it until then.  Contract: the array must not be written to between this call and
-        that upload - the upload is recognised by pointer, shape and scaling, and the copy already on the device is
-        used as it is."""
-        if not (isinstance(x, np.ndarray) and x.dtype in (np.float64, np.float32) and x.flags["C_CONTIGUOUS"] and x.ndim == 2):
-            raise ValueError("points_prefetch needs a C-contiguous float64 or float32 [n, d] array (it is not copied)")
-        if x.shape[0] == 0:
+        array (C-contiguous float64 or float32, or one points_view accepts) that is later passed to points_upload /
+        points_upload_scaled / online; the handle keeps a reference to it until then.  Contract: the array must not be
+        written to between this call and that upload - the upload is recognised by pointer, shape, layout, element type and
+        scaling, and the copy already on the device is used as it is."""
+        if isinstance(x, np.ndarray) and x.ndim == 2 and x.shape[0] == 0:
             return
+        src, view = points_source(x)
+        if src is not x or x.ndim != 2:
+            raise ValueError("points_prefetch needs an [n, d] array that is taken as it lies - C-contiguous float64 or float32, "
+                             "or a layout and element type points_view accepts (it is not copied)")
         scale = None if scale is None else _f64(scale)
         min_ = None if min_ is None else _f64(min_)
         self._prefetched = (x, scale, min_)  # keeps the buffers alive while the worker reads them
-        if x.dtype == np.float32:
+        if view is not None:
+            self._check(self._lib.cc_points_prefetch_view(self._h, C.byref(view), _ptr(scale), _ptr(min_)))
+        elif x.dtype == np.float32:
             self._check(self._lib.cc_points_prefetch_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(scale), _ptr(min_)))
         else:
             self._check(self._lib.cc_points_prefetch(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(scale), _ptr(min_)))
 
     def col_minmax(self, x):
         """Per-column (min, max) of x, NaN ignored, reduced on the device."""
-        x = as_points(x)
+        x, view = points_source(x)
         mn = np.empty(x.shape[1], dtype=np.float64)
         mx = np.empty(x.shape[1], dtype=np.float64)
-        if x.dtype == np.float32:
+        if view is not None:
+            self._check(self._lib.cc_col_minmax_view(self._h, C.byref(view), _ptr(mn), _ptr(mx)))
+        elif x.dtype == np.float32:
             self._check(self._lib.cc_col_minmax_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(mn), _ptr(mx)))
         else:
             self._check(self._lib.cc_col_minmax(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(mn), _ptr(mx)))
@@ -476,11 +544,13 @@ class Handle(object):
 
     def points_upload_scaled(self, x, scale, min_):
         """points_upload of x * scale + min_ (MinMaxScaler.transform), scaled on the device."""
-        x, scale, min_ = as_points(x), _f64(scale), _f64(min_)
+        (x, view), scale, min_ = points_source(x), _f64(scale), _f64(min_)
         if x.ndim != 2 or scale.shape != (x.shape[1],) or min_.shape != (x.shape[1],):
             raise ValueError("points must be [n, d], scale and min_ [d]")
         try:
-            if x.dtype == np.float32:
+            if view is not None:
+                self._check(self._lib.cc_points_upload_view(self._h, C.byref(view), _ptr(scale), _ptr(min_)))
+            elif x.dtype == np.float32:
                 self._check(self._lib.cc_points_upload_scaled_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(scale),
                                                                   _ptr(min_)))
             else:
@@ -525,14 +595,16 @@ class Handle(object):
         the table as it stands - (uid, path, dist): the creation number of the microcluster it would join (-1: it would
         create one), 0 pcore / 1 outlier / 5 outlier that the add promotes / 2 new, the projected distance to that
         microcluster (-1.0 for path 2); path and dist are None unless wanted.  Nothing of the handle changes."""
-        x = as_points(x)
+        x, view = points_source(x)
         if x.ndim != 2:
             raise ValueError("points must be a 2-d array")
         n = x.shape[0]
         uid = np.empty(n, dtype=np.int64)
         path = np.empty(n, dtype=np.int8) if want_path else None
         dist = np.empty(n, dtype=np.float64) if want_dist else None
-        if x.dtype == np.float32:
+        if view is not None:
+            self._check(self._lib.cc_assign_view(self._h, C.byref(view), _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
+        elif x.dtype == np.float32:
             self._check(self._lib.cc_assign_f32(self._h, _ptr(x, _fp), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
         else:
             self._check(self._lib.cc_assign(self._h, _ptr(x), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
@@ -670,6 +742,7 @@ class Handle(object):
         self._check(self._lib.cc_get_stats(self._h, C.byref(s)))
         out = {k: getattr(s, k) for k, _ in CcStats._fields_ if k != "reserved"}
         out["f32_points"] = self.f32_points()
+        out["view_points"] = self.view_points()
         return out
 
     def f32_points(self):
@@ -677,4 +750,11 @@ class Handle(object):
         prefetches and assigns of float32 arrays.  stats() carries it as "f32_points" beside the fields of cc_stats."""
         n = C.c_int64()
         self._check(self._lib.cc_f32_points(self._h, C.byref(n)))
+        return n.value
+
+    def view_points(self):
+        """Points this handle has taken through the `_view` entry points since it was created (cc_view_points): uploads,
+        adopted prefetches and assigns of arrays read where they lie.  stats() carries it as "view_points"."""
+        n = C.c_int64()
+        self._check(self._lib.cc_view_points(self._h, C.byref(n)))
         return n.value

@@ -127,7 +127,7 @@ class HDDStream(object):
                                         device_scaling=None):
         """device_scaling=(scale_, min_): `input_dataset` holds raw values and MinMaxScaler.transform
         (X * scale_ + min_) is applied on the device during the upload (scaling/scaler.py:39-41)."""
-        X = _lib.as_points(input_dataset)  # (a C-contiguous float32 array as it is: the device widens it)
+        X = _lib.points_source(input_dataset)[0]  # (an array the library reads where it lies stays as it is: the device widens it)
         if X.ndim != 2:
             raise ValueError("input_dataset must be 2-d [N, d]")
         if reset_param:
@@ -181,7 +181,7 @@ class HDDStream(object):
         current one.  Returns the array to pass to online_microcluster_maintenance (the same buffer, so that the upload
         is recognised); results never depend on whether a timepoint was prefetched.  The returned array must not be
         modified before it is passed on: the device copy made here is the one that gets clustered."""
-        X = _lib.as_points(input_dataset)
+        X = _lib.points_source(input_dataset)[0]
         if X.ndim == 2 and X.shape[0] > 0:
             if device_scaling is None:
                 self._h.points_prefetch(X)
@@ -268,7 +268,7 @@ class HDDStream(object):
         (uid, path) with uid the creation number of the microcluster it would join (-1: it would create one) and path 0
         pcore / 1 outlier / 5 outlier that the add would promote / 2 new.  Every point is scored on its own against the
         microclusters as they stand; nothing of the model changes (Handle.assign)."""
-        X = _lib.as_points(input_dataset)
+        X = _lib.points_source(input_dataset)[0]
         if X.ndim != 2:
             raise ValueError("input_dataset must be 2-d [N, d]")
         self._assign_params()
@@ -353,7 +353,7 @@ class HDDStream(object):
         if self.labels_uid is None or self._X is None:
             return {}
         if self._X.dtype != np.float64:
-            self._X = self._X.astype(np.float64)  # (single-precision input: widened on demand, what the device holds)
+            self._X = self._X.astype(np.float64)  # (narrow-typed input: widened on demand, what the device holds)
         if self._uid_rows is None:
             order = np.argsort(self.labels_uid, kind="stable")
             keys, starts = np.unique(self.labels_uid[order], return_index=True)

@@ -383,10 +383,11 @@ Rows padded_rows(cc_handle* h, hipStream_t st, Rows rows, int q, int round, int 
 
 }  // namespace
 
-// one online call (OnlineRun, online_range), then the entry points by concern: points, offline phase and tracker, multi-GPU,
+// one online call (OnlineRun, online_range), then the entry points by concern: points, point views, offline phase and tracker, multi-GPU,
 // read-only assignment
 #include "cc_online_run.h"
 #include "cc_api_points.inc"
+#include "cc_api_views.inc"
 #include "cc_api_offline.inc"
 #include "cc_api_comm.inc"
 #include "cc_api_assign.inc"
@@ -732,6 +733,13 @@ int cc_f32_points(cc_handle* h, int64_t* out)
 {
     if (!h || !out) return CC_ERR_BAD_ARG;
     *out = h->f32_points;
+    return CC_OK;
+}
+
+int cc_view_points(cc_handle* h, int64_t* out)
+{
+    if (!h || !out) return CC_ERR_BAD_ARG;
+    *out = h->view_points;
     return CC_OK;
 }
 

@@ -321,6 +321,7 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
     DevBuf<double> scr, scr2;  // scaler scratch
     DevBuf<float> ingest_raw[2];  // cc_points_upload_f32: the two slabs of raw single-precision points (k_ingest_f32 reads them)
     long long f32_points = 0;     // cc_f32_points: points taken in single precision since cc_create
+    long long view_points = 0;    // cc_view_points: points taken through the `_view` entry points since cc_create (they share ingest_raw, in bytes)
 
     // cc_points_prefetch: the next timepoint's points, uploaded by a worker thread through page-locked staging
     struct Prefetch {
@@ -332,6 +333,9 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
         bool scaled = false;
         bool f32 = false;               // x is float, staged piece by piece into raw[] and taken in by k_ingest_f32
         long long piece = 0;            // ... points per piece: whole 64-point tiles that fit a page-locked buffer
+        bool view = false;              // x is element (0, 0) of a cc_points_view of this dtype and these strides (k_ingest; pieces as for f32)
+        int dtype = 0;
+        long long rs = 0, cs = 0;
         DevBuf<float> raw[2];
         std::vector<double> scale, mn;
         DevBuf<double> X, Xt, sm;       // destination buffers (swapped with the handle's on adoption), scale / min

@@ -231,3 +231,4 @@ __device__ __forceinline__ double cc_sel_scale(unsigned mask, double scaled, dou
 #include "cc_seq_g.h"     // ... and on the table in HBM, one workgroup: tables beyond the LDS image
 #include "cc_relaxed.h"   // relaxed multi-GPU mode
 #include "cc_points.h"    // transposed copy, finiteness check, scaler
+#include "cc_ingest.h"    // the fused ingest of a point view: any accepted element type, rows or columns

@@ -8,6 +8,8 @@ tests/test_host_logic.py checks bit equality against scikit-learn."""
 import numpy as np
 import pandas as pd
 
+from .._lib import points_source
+
 
 def read_timepoint(filename):
     """One timepoint as float64 [N, d].  CSV with a header row as in the reference (app.py:170, scaler.py:31);
@@ -31,9 +33,9 @@ class Scaler(object):
         if data_files is not None and handle is not None:
             lo = hi = None
             for filename in data_files:
-                X = read_timepoint(filename)
-                if X.dtype != np.float32:
-                    X = np.ascontiguousarray(X, dtype=np.float64)
+                # (kept as parsed where the library reads it where it lies - pandas hands a CSV out column-major -, else as
+                # a C-contiguous float64 copy)
+                X = points_source(read_timepoint(filename))[0]
                 self.parsed[filename] = X
                 if X.shape[0] == 0:
                     continue

@@ -12,7 +12,9 @@
  *  - plain C: pointers + sizes, no C++/torch types; every function returns 0
  *    on success or a negative cc_status; cc_last_error() has the text;
  *  - host pointers unless the name says "device"; row-major float64 [N, d]
- *    (the `_f32` entry points: row-major float32 [N, d], widened on the device);
+ *    (the `_f32` entry points: row-major float32 [N, d], widened on the device;
+ *    the `_view` entry points: a cc_points_view - rows or columns, nine element
+ *    types -, widened on the device);
  *  - one handle = one HDDStream state on one GPU; a handle is not thread-safe;
  *  - all floating-point work is IEEE double, no FMA contraction, sums over
  *    dimensions strictly left to right, so results are bit-identical to the
@@ -236,6 +238,53 @@ int cc_assign_f32(cc_handle* h, const float* x, int64_t n, int32_t d, int64_t* o
  * rows = the padded scan width (cc_scan_width) for 9 <= d <= CC_WINDOW_MAX_DIM, else d; the rows beyond d hold +0.0. */
 int cc_points_download_xt(cc_handle* h, double* out);
 int cc_f32_points(cc_handle* h, int64_t* out);
+
+/* Point views: points where they lie - column-major, pitched or narrow-typed - without a copy on the host.  Strides are in
+ * ELEMENTS, not bytes; the elements are in native byte order. */
+enum cc_dtype {
+    CC_DT_F64 = 0, CC_DT_F32 = 1, CC_DT_F16 = 2,   /* IEEE binary64 / binary32 / binary16 */
+    CC_DT_I8 = 3, CC_DT_U8 = 4, CC_DT_I16 = 5, CC_DT_U16 = 6, CC_DT_I32 = 7, CC_DT_U32 = 8
+};
+
+typedef struct cc_points_view {
+    const void* data;     /* element (0, 0) */
+    int64_t n;            /* points */
+    int32_t d;            /* dimensions */
+    int32_t dtype;        /* CC_DT_F64, _F32, _F16, _I8, _U8, _I16, _U16, _I32, _U32: native byte order */
+    int64_t row_stride;   /* elements from a point to the next */
+    int64_t col_stride;   /* elements from a dimension to the next */
+} cc_points_view;
+
+/* A view is taken in one of two layouts:
+ *   rows form:    col_stride == 1 && row_stride >= d  (C order; a range of columns of a C-order array)
+ *   columns form: row_stride == 1 && col_stride >= n  (Fortran order - what pandas hands out for a parsed CSV -; a range
+ *                 of rows of a Fortran-order array; the transpose of a [d, N] array)
+ * (The stride of an axis of length 1 says nothing and is ignored: one point or one dimension satisfies both, and is taken in
+ * the rows form.)  Every other view - a zero or negative stride, both strides different
+ * from 1, an unknown dtype, d outside 1..CC_MAX_DIM, an extent beyond int64 - is refused with CC_ERR_BAD_ARG and a message
+ * that names the reason, before anything is read, launched or allocated.
+ * Each entry point has the contract of its float64 sibling.  The bytes cross the bus as they are, in slabs of whole 64-point
+ * tiles through the two device staging buffers of the `_f32` route (at most 32 MiB each, 16 MiB pieces in a prefetch;
+ * CHRONOCLUST_HIP_INGEST_SLAB=<points> shortens a slab): the rows form as whole pitched rows in one copy (a pitch beyond 8 d
+ * elements is stripped on the host, slab by slab, in elements of the source type), the columns form as d strips.  One kernel
+ * per slab (k_ingest) widens - (double) of every accepted type is exact -, applies scale_ / min_ in double (two roundings),
+ * checks the stored values for NaN / Inf and writes the row-major and the dimension-major copy: what the device then holds is
+ * bit for bit what cc_points_upload holds after the same values widened and laid out on the host.
+ * cc_points_upload_view / cc_points_prefetch_view: scale and min_ both NULL (plain) or both given (cc_points_upload_scaled).
+ * A prefetch is adopted by the cc_points_upload_view (or cc_online_view) of the same pointer, shape, both strides, dtype and
+ * scaling; any other upload discards it.
+ * cc_col_minmax_view: the extrema compare equal to cc_col_minmax of the widened dense array (the sign of a zero extremum may
+ * differ: the reduction's order does; MinMaxScaler's scale_ and min_ are the same for both signs).
+ * cc_assign_view takes the chunks cc_assign takes (cc_stats.assign_launches is the same), each through sub-slabs of at most
+ * 16 MiB of staging; cc_col_minmax_view reduces the upload's slabs in the upload's staging buffers: no staging is added.
+ * cc_view_points: *out = the points taken through the `_view` entry points since cc_create (uploads, an adopted prefetch
+ * included, cc_online_view, cc_assign_view); no call clears it.  cc_f32_points counts the `_f32` entry points only. */
+int cc_points_upload_view(cc_handle* h, const cc_points_view* view, const double* scale, const double* min_);
+int cc_points_prefetch_view(cc_handle* h, const cc_points_view* view, const double* scale, const double* min_);
+int cc_col_minmax_view(cc_handle* h, const cc_points_view* view, double* out_min, double* out_max);
+int cc_online_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path);
+int cc_assign_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path, double* out_dist);
+int cc_view_points(cc_handle* h, int64_t* out);
 
 /* HDDStream.pcore_MC / outlier_MC (hddstream.py:56-57) in list order.
  * Any output pointer may be NULL.  cf1/cf2/cen/pref are [count, d]. */
