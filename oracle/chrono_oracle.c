@@ -42,7 +42,9 @@ typedef struct {
     double ups_eps_sq;  /* predecon.py:40   (upsilon*epsilon) ** 2            */
     double delta;       /* predecon.py:42   delta (NOT squared, predecon:213) */
     int32_t pi;         /* hddstream.py:107-114                               */
-    int32_t pad;
+    int32_t no_create;  /* (was padding; 0 = the reference) 1: a point that no microcluster absorbs creates none and
+                         * leaves the lists untouched: uid -1, path 8 - phase A of the relaxed multi-GPU mode's model
+                         * (tests/relaxed_model.py); not the reference's behaviour */
 } co_params;
 
 typedef struct {
@@ -240,6 +242,14 @@ int co_inject_mc(co_state *s, int kind, int d, const double *cf1, const double *
     return 0;
 }
 
+/* The two id counters as given: co_inject_mc derives them from the largest id it has seen, a table that continues a
+ * stream carries its own (test infrastructure: tests/relaxed_model.py). */
+void co_set_counters(co_state *s, int64_t pcore_last_id, int64_t outlier_last_id)
+{
+    s->pcore_last_id = pcore_last_id;
+    s->outlier_last_id = outlier_last_id;
+}
+
 /* ------------------------------------------------------------------ */
 /* decay + downgrade  (hddstream.py:199-213, 247-286, 512-549)         */
 /* ------------------------------------------------------------------ */
@@ -391,6 +401,11 @@ int co_online(co_state *s, const double *X, int64_t N, int d, int64_t *out_uid, 
                     done = 1;
                 }
             }
+        }
+        if (!done && s->p.no_create) { /* not the reference: see co_params */
+            out_uid[r] = -1;
+            if (out_path) out_path[r] = 8;
+            done = 1;
         }
         /* ---- _create_new_outlier_cluster, hddstream.py:434-462 ---- */
         if (!done) {

@@ -9,6 +9,12 @@ dataset-dependent parameters, decay + downgrade when the daystamp changes, the
 per-point online loop, then the offline PreDeCon phase.  Parameter derivation
 uses the reference's own Python expressions so that the C side only ever sees
 finished doubles.
+
+Two additions serve the model of the relaxed multi-GPU mode (tests/relaxed_model.py) and nothing else; neither is the
+reference's, and both are off unless asked for: `OracleHDDStream.no_create` (the former padding of co_params: a point that
+no microcluster absorbs gets uid -1 and path 8 and leaves the lists untouched instead of creating an outlier
+microcluster) and `OracleHDDStream.set_counters` (co_set_counters: the two id counters as given, where co_inject_mc
+derives them from the largest id it has seen).
 """
 import ctypes as C
 import os
@@ -25,7 +31,7 @@ PCORE, OUTLIER = 0, 1
 class CoParams(C.Structure):
     _fields_ = [("eps_sq", C.c_double), ("delta_sq", C.c_double), ("k", C.c_double), ("beta", C.c_double),
                 ("mu", C.c_double), ("omicron", C.c_double), ("ups_eps", C.c_double),
-                ("ups_eps_sq", C.c_double), ("delta", C.c_double), ("pi", C.c_int32), ("pad", C.c_int32)]
+                ("ups_eps_sq", C.c_double), ("delta", C.c_double), ("pi", C.c_int32), ("no_create", C.c_int32)]
 
 
 def build(force=False):
@@ -48,6 +54,8 @@ def lib():
         L.co_destroy.argtypes = [C.c_void_p]
         L.co_set_params.argtypes = [C.c_void_p, C.POINTER(CoParams)]
         L.co_inject_mc.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp, dp, dp, C.c_double, C.c_int64, C.c_int64]
+        L.co_set_counters.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+        L.co_set_counters.restype = None
         L.co_decay_downgrade.argtypes = [C.c_void_p, C.c_double]
         L.co_online.argtypes = [C.c_void_p, dp, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int8)]
         L.co_count.argtypes = [C.c_void_p, C.c_int]
@@ -163,6 +171,7 @@ class OracleHDDStream(object):
         self._h = C.c_void_p(lib().co_create())
         self.labels_uid = None
         self.paths = None
+        self.no_create = False  # True: co_online creates no microcluster (uid -1, path 8); see the module docstring
 
     def __del__(self):
         try:
@@ -174,7 +183,7 @@ class OracleHDDStream(object):
 
     def _push_params(self):
         p = CoParams(self.epsilon_squared, self.delta_squared, self.k, self.beta, float(self.mu),
-                     float(self.omicron), self.upsilon, self.upsilon ** 2, self.delta, int(self.pi), 0)
+                     float(self.omicron), self.upsilon, self.upsilon ** 2, self.delta, int(self.pi), int(bool(self.no_create)))
         lib().co_set_params(self._h, C.byref(p))
 
     def set_dataset_dependent_parameters(self, X):
@@ -234,6 +243,9 @@ class OracleHDDStream(object):
         L.co_export(self._h, kind, out['id'].ctypes.data_as(i64), out['uid'].ctypes.data_as(i64), _dp(out['w']),
                     _dp(out['cf1']), _dp(out['cf2']), _dp(out['cen']), _dp(out['pref']))
         return out
+
+    def set_counters(self, pcore_last_id, outlier_last_id):
+        lib().co_set_counters(self._h, int(pcore_last_id), int(outlier_last_id))
 
     @property
     def counters(self):

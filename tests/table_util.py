@@ -921,6 +921,446 @@ def build_online(name):
     return gen(**kw)
 
 
+# ---- the relaxed multi-GPU mode on injected tables ----------------------------------------------------------------------
+#
+# Cases for tests/relaxed_model.py (the CPU model of cc_comm_set_relaxed) and tests/test_relaxed_model.py (the library against
+# it): (pcores, outliers, params, X, meta) as above; meta carries `world` and `minibatch`, the group the points were laid out
+# for - X is world blocks of ceil(n / world) points, block r being rank r's shard.  `check_relaxed` asserts on the MODEL's
+# result that what a case exists for happened.
+
+def _lattice_sites(rng, n, d, spacing=0.6):
+    """n distinct sites of a grid of the given spacing in the first min(d, 8) dimensions (the further dimensions uniform in
+    [0.1, 0.9)), in random order, each moved by up to a thousandth of the spacing: `spacing` apart or more.  At 0.6 a row of
+    weight up to 140 refuses a point of the next site (tentative variance 0.36 w / (w + 1)^2 > 0.0025 = eps_sq)."""
+    f = min(d, 8)
+    base = 2
+    while base ** f < n:
+        base += 1
+    cell = rng.choice(base ** f, n, replace=False)
+    out = rng.uniform(0.1, 0.9, (n, d))
+    for i in range(f):
+        out[:, i] = 0.1 + spacing * ((cell // base ** i) % base)
+    out[:, :f] += rng.uniform(-1e-3, 1e-3, (n, f)) * spacing
+    return out
+
+
+def _shards(blocks):
+    """Rank r's points are blocks[r] (equal lengths): the array the group clusters."""
+    assert len({len(b) for b in blocks}) == 1
+    return np.ascontiguousarray(np.concatenate(blocks))
+
+
+def relaxed_promotions(seed, d, world=3, per_rank=2500, m_p=100, m_o=2000, minibatch=2500):
+    """Promotions the merge makes and no rank made, and the reverse: m_p pcores and m_o outliers on lattice sites 0.6 apart,
+    every stored entry k, variances tiny, outlier weights cycling through beta mu - 1, - 2, - 3 (beta mu = 8).  Every rank's shard
+    holds one point near outlier j where j % 7 == 0 or j % 14 == 1 (all ranks together lift weights 6 and 5 to beta mu where
+    world >= 3, a rank alone only weight 7), rank (j // 7) % world alone one near outlier j where j % 7 == 3, points near the
+    pcores, and `far` points near a dozen sites that hold no row (set aside; phase B creates their microclusters).  Outliers j with
+    j % 7 == 5 weigh beta mu + 2 and absorb nothing (a stream leaves such rows behind when mu = mu_cfg N falls from one timepoint
+    to the next): only rows that absorbed a point in the super-step are promoted.  With
+    m_p + m_o = 2 100 rows each of k_rel_promote's 1 024 threads owns three rows, and outliers j, j + 1 share a thread."""
+    rng = np.random.default_rng(seed)
+    k, beta, mu = 4.0, 0.5, 16.0
+    sites = _lattice_sites(rng, m_p + m_o + 12, d)
+    cp, co, cfar = sites[:m_p], sites[m_p:m_p + m_o], sites[m_p + m_o:]
+    pcores = _table(rng, cp, rng.uniform(0.0, 1e-8, (m_p, d)), k, rng.uniform(10.0, 40.0, m_p))
+    j = np.arange(m_o)
+    w_o = beta * mu - 1.0 - (j % 3)
+    w_o[j % 7 == 5] = beta * mu + 2.0                          # heavy, and no point comes near them: they stay outliers
+    outliers = _outlier_table(rng, co, rng.uniform(0.0, 1e-8, (m_o, d)), k, w_o)
+    every = j[(j % 7 == 0) | (j % 14 == 1)]
+    blocks = []
+    for r in range(world):
+        own = j[(j % 7 == 3) & ((j // 7) % world == r)]
+        near_o = np.concatenate([every, own])
+        n_far = min(100, max(0, per_rank - len(near_o)) // 4)
+        n_p = per_rank - len(near_o) - n_far
+        assert n_p >= 0, "a shard of %d points has no room for %d outlier sites" % (per_rank, len(near_o))
+        base = np.concatenate([co[near_o], cp[rng.integers(0, m_p, n_p)], cfar[rng.integers(0, len(cfar), n_far)]])
+        blocks.append((base + rng.normal(0.0, 0.002, base.shape))[rng.permutation(per_rank)])
+    par = Params(0.05 ** 2, 0.05 ** 2, k, beta, mu, 0.1, 0.5, 0.25, 0.05, d)
+    meta = dict(kind="relaxed-promotions", tainted=False, world=world, minibatch=minibatch, full=m_p + m_o > 2048 and world >= 3)
+    return pcores, outliers, par, _shards(blocks), meta
+
+
+def relaxed_divergence(seed, d, world=3, per_rank=100, groups=24, minibatch=64):
+    """A promotion a rank makes and the merge refuses, and the reverse.  pi = d - 1, eps 0.1, delta_sq 0.0025, beta mu = 8, outliers of
+    weight 7 on lattice sites 0.6 apart, three kinds, `groups` of each:
+      X  variance 1.2 delta_sq in dimension 0 (entry 1), tiny elsewhere (entries k): d - 1 entries above 1.  One point on the
+         centroid leaves 1.05 delta_sq - the rank promotes, its label carries 4 -, two or three leave 0.93 / 0.84 delta_sq: d
+         entries above 1, the merged row stays an outlier;
+      Y  variance 0.9 delta_sq in dimension 0 (d entries above 1).  One point at a = sqrt(1.85 delta_sq) beside the centroid in
+         dimension 0 leaves 0.990 delta_sq - heavy enough, too many entries -, two or three leave 1.020 / 1.019 delta_sq: d - 1
+         entries, the merge promotes by the entry count;
+      Z  plain (entries k but one, variance 2 delta_sq there): promoted by every rank that touches it.
+    Ranks 0 .. min(world, 3) - 1 hold one point for each X and Y row, every rank one for some Z rows and points near the pcores
+    (variance 2 delta_sq in dimension 0, so that the pdim filter lets points join them), a few far from everything."""
+    rng = np.random.default_rng(seed)
+    assert d >= 2
+    k, beta, mu, ds = 4.0, 0.5, 16.0, 0.05 ** 2
+    g, m_p = groups, 16
+    sites = _lattice_sites(rng, m_p + 3 * g + 4, d)
+    cp, co, cfar = sites[:m_p], sites[m_p:m_p + 3 * g], sites[m_p + 3 * g:]
+    var_p = rng.uniform(0.0, 1e-8, (m_p, d))
+    var_p[:, 0] = 2.0 * ds
+    pref_p = np.full((m_p, d), k)
+    pref_p[:, 0] = 1.0
+    pcores = _table(rng, cp, var_p, pref_p, rng.uniform(10.0, 30.0, m_p))
+    perm = rng.permutation(3 * g)
+    kind = perm % 3                                          # 0 X, 1 Y, 2 Z, in list order at random
+    var = rng.uniform(0.0, 1e-8, (3 * g, d))
+    var[:, 0] = np.array([1.2, 0.9, 2.0])[kind] * ds
+    pref = np.full((3 * g, d), k)
+    pref[kind != 1, 0] = 1.0
+    outliers = _outlier_table(rng, co, var, pref, np.full(3 * g, beta * mu - 1.0))
+    a = np.sqrt(1.85 * ds)
+    x_rows, y_rows, z_rows = (np.flatnonzero(kind == i) for i in range(3))
+    sharing = min(world, 3)
+    blocks = []
+    for r in range(world):
+        pts = []
+        if r < sharing:
+            pts.append(co[x_rows])
+            py = co[y_rows].copy()
+            py[:, 0] += a
+            pts.append(py)
+        pts.append(co[z_rows[r % 2::2]])
+        n_far = 4
+        pts.append(cfar[rng.integers(0, len(cfar), n_far)] + rng.normal(0.0, 1e-3, (n_far, d)))
+        have = sum(len(x) for x in pts)
+        assert have <= per_rank
+        pts.append(cp[rng.integers(0, m_p, per_rank - have)] + rng.normal(0.0, 1e-3, (per_rank - have, d)))
+        blocks.append(np.concatenate(pts)[rng.permutation(per_rank)])
+    par = Params(0.1 ** 2, ds, k, beta, mu, 0.1, 0.5, 0.25, 0.05, d - 1)
+    meta = dict(kind="relaxed-divergence", tainted=False, world=world, minibatch=minibatch, x_uid=outliers.uid[x_rows],
+                y_uid=outliers.uid[y_rows])
+    return pcores, outliers, par, _shards(blocks), meta
+
+
+def relaxed_compaction(seed, d, world=3, per_rank=2500, minibatch=2500, first=0):
+    """Set-aside points on the pass and wave boundaries of k_rel_collect (1 024 points per pass, 16 waves of 64): 50 pcores and
+    20 outliers on lattice sites; rank 0 sets aside its points at `first` + 0, 63, 64, 1 023, 1 024, 2 047, 2 048 and 2 499 (those its
+    shard has), rank 1 nothing, rank 2 everything in the first super-step (where `first` is 0), further ranks as rank 0.
+    Set-aside points of the first super-step that has any lie near six sites that hold no row: the first of a site creates a
+    microcluster in phase B, the others - of whichever rank - join it, and so do rank 2's points of later mini-batches, in
+    phase A.  The edge positions of later super-steps have a site each.  Mini-batches start at 2 048 points and double up to the
+    configured size: with 2 500, `first` = 2 048 puts the positions into the second super-step, the first of 2 500 points
+    (three passes), while at `first` = 0 positions 0 .. 2 047 end the two passes of the first one."""
+    rng = np.random.default_rng(seed)
+    k, beta, mu = 4.0, 0.5, 16.0
+    m_p, m_o, n_new = 50, 20, 6
+    edges = np.array([p for p in (0, 63, 64, 1023, 1024, 2047, 2048, 2499) if first + p < per_rank], np.int64) + first
+    bounds, pos, size = [], 0, min(minibatch, 2048)
+    while pos < per_rank:
+        bounds.append(min(per_rank, pos + size))
+        pos, size = pos + size, min(minibatch, size * 2)
+    step_of = np.searchsorted(np.array(bounds), edges, side="right")
+    late = edges[step_of > step_of.min()]
+    sites = _lattice_sites(rng, m_p + m_o + n_new + world * len(late), d)
+    cp, co, cnew, clate = sites[:m_p], sites[m_p:m_p + m_o], sites[m_p + m_o:m_p + m_o + n_new], sites[m_p + m_o + n_new:]
+    pcores = _table(rng, cp, rng.uniform(0.0, 1e-8, (m_p, d)), k, rng.uniform(10.0, 40.0, m_p))
+    outliers = _outlier_table(rng, co, rng.uniform(0.0, 1e-8, (m_o, d)), k, rng.uniform(1.0, 3.0, m_o))
+    blocks, aside = [], []
+    for r in range(world):
+        mask = np.zeros(per_rank, bool)
+        if r == 2:
+            mask[:] = True
+        elif r != 1:
+            mask[edges] = True
+        base = np.where(mask[:, None], cnew[rng.integers(0, n_new, per_rank)],
+                        np.concatenate([cp, co])[rng.integers(0, m_p + m_o, per_rank)])
+        if r == 2:                                           # (only the first mini-batch's are set aside; see above)
+            mask[:] = False
+            mask[:bounds[0]] = first == 0
+        elif r != 1:
+            base[late] = clate[r * len(late):(r + 1) * len(late)]
+        blocks.append(base + rng.normal(0.0, 0.002, base.shape))
+        aside.append(np.flatnonzero(mask) + r * per_rank)
+    par = Params(0.05 ** 2, 0.05 ** 2, k, beta, mu, 0.1, 0.5, 0.25, 0.05, d)
+    meta = dict(kind="relaxed-compaction", tainted=False, world=world, minibatch=minibatch, aside=np.concatenate(aside))
+    return pcores, outliers, par, _shards(blocks), meta
+
+
+def relaxed_moving(seed, d, world=2, per_rank=2304, m_p=2048, pairs=64, minibatch=256):
+    """Centroids that a merge moves past a neighbouring row: m_p pcores (every entry k, variances tiny), among them `pairs` pairs
+    (A, B) with B = A - g e_0, g = 0.02, A of weight 2.  Pair p is served in super-step s = 1 + p % (steps - 2): every rank's
+    mini-batch s holds ceil(6 / world) points at A + 1.5 g e_0 (A takes them and ends beyond A + g e_0 in the merge), and
+    mini-batch s + 1 of rank p % world holds a probe at A - 0.4 g e_0: A is its nearest row in the table before that merge, B in
+    the table after it.  The other points lie near pcores chosen at random.  eps 0.05: every radius test passes."""
+    rng = np.random.default_rng(seed)
+    k, beta, mu, g = 4.0, 0.5, 16.0, 0.02
+    cen = _lattice_sites(rng, m_p, d) if d < 14 else rng.uniform(0.1, 0.9, (m_p, d))
+    w = rng.uniform(10.0, 40.0, m_p)
+    A, B = np.arange(pairs), pairs + np.arange(pairs)
+    cen[B] = cen[A]
+    cen[B, 0] -= g
+    w[A] = 2.0
+    order = rng.permutation(m_p)
+    row_of = np.empty(m_p, np.int64)
+    row_of[order] = np.arange(m_p)
+    pcores = _table(rng, cen[order], rng.uniform(0.0, 1e-8, (m_p, d)), k, w[order])
+    steps = []
+    pos, size = 0, min(minibatch, 2048)
+    while pos < per_rank:
+        steps.append((pos, min(per_rank, pos + size)))
+        pos, size = pos + size, min(minibatch, size * 2)
+    assert len(steps) >= 4
+    each = -(-6 // world)
+    planned = [[[] for _ in steps] for _ in range(world)]
+    e0 = np.zeros(d)
+    e0[0] = 1.0
+    for p in range(pairs):
+        s = 1 + p % (len(steps) - 2)
+        for r in range(world):
+            planned[r][s] += [cen[A[p]] + 1.5 * g * e0] * each
+        planned[p % world][s + 1].append(cen[A[p]] - 0.4 * g * e0)
+    blocks = []
+    for r in range(world):
+        out = []
+        for (a, e), special in zip(steps, planned[r]):
+            assert len(special) <= e - a
+            fill = cen[pairs * 2 + rng.integers(0, m_p - 2 * pairs, e - a - len(special))]
+            fill = fill + rng.normal(0.0, 0.002, fill.shape)
+            batch = np.concatenate([np.array(special).reshape(-1, d), fill])
+            out.append(batch[rng.permutation(e - a)])
+        blocks.append(np.concatenate(out))
+    par = Params(0.05 ** 2, 0.05 ** 2, k, beta, mu, 0.1, 0.5, 0.25, 0.05, d)
+    meta = dict(kind="relaxed-moving", tainted=False, world=world, minibatch=minibatch, A=pcores.uid[row_of[A]],
+                B=pcores.uid[row_of[B]])
+    return pcores, None, par, _shards(blocks), meta
+
+
+def relaxed_threshold(seed, d, world=2, per_rank=64, rows=16, minibatch=64):
+    """Merged variances exactly ON delta_sq.  delta_sq = 1/16, eps 1/2; `rows` pcores and as many outliers of weight 2 whose
+    centroid is 8 + 2 i in dimension 0 (far from every other row, which lie on lattice sites below 4) with variance 1/16 there.
+    Rank 0 holds a point 1/4 above each such centroid, rank 1 one 1/4 below: alone either leaves 1/16 - 1/144, together W = 4,
+    CF1 / W the old centroid and CF2 / W - (CF1 / W)^2 = 1/16 - every term a small dyadic number, every sum exact -, so the merged
+    entry is k by `<=` and would be 1 by `<`.  Further ranks and the other points: near plain pcores."""
+    rng = np.random.default_rng(seed)
+    assert world >= 2 and d >= 2
+    k, beta, mu = 4.0, 0.5, 16.0
+    m_plain = 8
+    sites = _lattice_sites(rng, m_plain + 2 * rows, d)
+    cen = sites.copy()
+    cen[m_plain:, 0] = 8.0 + 2.0 * np.arange(2 * rows)
+    var = rng.uniform(0.0, 1e-8, (m_plain + 2 * rows, d))
+    var[m_plain:, 0] = 1.0 / 16.0
+    w = np.concatenate([rng.uniform(10.0, 40.0, m_plain), np.full(2 * rows, 2.0)])
+    on_p = np.arange(m_plain + rows)
+    on_o = m_plain + rows + np.arange(rows)
+    pcores = _table(rng, cen[on_p], var[on_p], k, w[on_p])
+    outliers = _outlier_table(rng, cen[on_o], var[on_o], k, w[on_o])
+    blocks = []
+    for r in range(world):
+        pts = []
+        if r < 2:
+            x = cen[m_plain:].copy()
+            x[:, 0] += 0.25 if r == 0 else -0.25
+            pts.append(x)
+        have = sum(len(x) for x in pts)
+        assert have <= per_rank
+        pts.append(cen[rng.integers(0, m_plain, per_rank - have)] + rng.normal(0.0, 1e-3, (per_rank - have, d)))
+        blocks.append(np.concatenate(pts)[rng.permutation(per_rank)])
+    par = Params(0.25, 1.0 / 16.0, k, beta, mu, 0.1, 0.5, 0.25, 0.05, d)
+    meta = dict(kind="relaxed-threshold", tainted=False, world=world, minibatch=minibatch,
+                uids=np.concatenate([pcores.uid[m_plain:], outliers.uid]))
+    return pcores, outliers, par, _shards(blocks), meta
+
+
+def relaxed_tainted(seed, d, world=2, minibatch=64, m_p=60, m_o=60, n=300, **kw):
+    """`stale` as the relaxed mode sees it: stored entries that disagree with the variances (the handle is tainted).  A row that
+    absorbs a point on any rank gets entries of k and 1 in the merge; a row that absorbs none keeps its stored ones."""
+    pcores, outliers, par, X, meta = stale(seed, m_p, m_o, d, n, **kw)
+    meta = dict(meta, kind="relaxed-tainted", world=world, minibatch=minibatch)
+    return pcores, outliers, par, X, meta
+
+
+def relaxed_victims(seed, d, world=3, minibatch=64, pairs=40, **kw):
+    pcores, outliers, par, X, meta = victims(seed, pairs, d, points=pairs // 2, **kw)
+    meta = dict(meta, kind="relaxed-tainted", world=world, minibatch=minibatch)
+    return pcores, outliers, par, X, meta
+
+
+def model_relaxed(case, world=None, minibatch=None):
+    """The model's side of a relaxed case (relaxed_model.relaxed_online on the injected tables); world / minibatch other than
+    the case's own run the same points in another group (the structure conditions then need not hold)."""
+    import relaxed_model as R
+    pcores, outliers, par, X, meta = case
+    state = R.state_of(make_oracle(par, pcores, outliers), X.shape[1])
+    return R.relaxed_online(par, state, X, world or meta["world"], minibatch or meta["minibatch"])
+
+
+def _nearest(X, t):
+    """Per point the uid of the nearest row of table t (projected distance, first minimum)."""
+    out = np.empty(len(X), np.int64)
+    for a in range(0, len(X), 64):
+        x = X[a:a + 64]
+        dist = ((x[:, None, :] - t["cen"][None, :, :]) ** 2 / t["pref"][None, :, :]).sum(axis=2)
+        out[a:a + 64] = t["uid"][dist.argmin(axis=1)]
+    return out
+
+
+def check_relaxed(case, res):
+    """Asserts on the MODEL's result that the case holds what it exists for (no GPU involved); returns the counts behind the
+    conditions."""
+    pcores, outliers, par, X, meta = case
+    kind, steps = meta["kind"], res["steps"]
+    counts = {}
+    local_up = [set() for _ in steps]                         # uids some rank promoted in phase A, per super-step
+    for s, st in enumerate(steps):
+        for lu, lp in st["local"]:
+            local_up[s] |= set(int(u) for u in lu[(lp >= 0) & (lp & 4 != 0) & (lp != 8)])
+    if kind == "relaxed-promotions":
+        info = steps[0]["info"]
+        m = len(info["w"])
+        per = -(-m // 1024)
+        rows = info["promoted"]
+        uids = [int(u) for u in info["rows"]["uid"][rows]]
+        merged_only = [u for u in uids if u not in local_up[0]]
+        threads = rows // per
+        idle_heavy = (~info["touched"]) & info["heavy"] & ((info["pref"] > 1.0).sum(axis=1) <= par.pi)
+        idle_heavy[:info["n_pcore"]] = False
+        kept = set(int(u) for u in res["state"]["outlier"]["uid"])
+        assert idle_heavy.sum() >= 8 and all(int(u) in kept for u in info["rows"]["uid"][idle_heavy]), int(idle_heavy.sum())
+        counts = dict(rows=m, rows_per_thread=per, promotions=len(rows), merged_only=len(merged_only),
+                      heavy_outliers_left_alone=int(idle_heavy.sum()),
+                      also_local=len(uids) - len(merged_only), threads=len(np.unique(threads)),
+                      pairs_in_a_thread=int((np.diff(threads) == 0).sum()), set_aside=res["stats"]["deferred_points"])
+        if meta["full"]:
+            assert per >= 3, counts
+            assert counts["merged_only"] >= 32 and counts["also_local"] >= 32, counts
+            assert counts["pairs_in_a_thread"] >= 1 and counts["threads"] >= 8, counts
+    elif kind == "relaxed-divergence":
+        outl = set(int(u) for u in res["state"]["outlier"]["uid"])
+        pc = set(int(u) for u in res["state"]["pcore"]["uid"])
+        all_local = set().union(*local_up)
+        refused = [int(u) for u in meta["x_uid"] if int(u) in all_local and int(u) in outl]
+        by_count = []
+        for s, st in enumerate(steps):
+            if st["info"] is None:
+                continue
+            info = st["info"]
+            beta_mu = par.beta * par.mu
+            heavy_somewhere = np.zeros(len(info["w"]), bool)
+            for dw in info["dw_by_rank"]:
+                heavy_somewhere |= (dw != 0.0) & (info["rows"]["w"] + dw >= beta_mu)
+            for r in info["promoted"]:
+                u = int(info["rows"]["uid"][r])
+                if u not in local_up[s] and heavy_somewhere[r]:
+                    by_count.append(u)
+        counts = dict(local_promotion_refused=len(refused), merged_by_entry_count=len(by_count),
+                      of_them_y=len(set(by_count) & set(int(u) for u in meta["y_uid"])))
+        if meta["world"] >= 2:
+            assert len(refused) >= 1 and len(by_count) >= 1 and set(by_count) <= pc, counts
+    elif kind == "relaxed-compaction":
+        aside = np.flatnonzero(np.isin(np.arange(len(X)), np.concatenate([st["deferred"] for st in steps])))
+        assert np.array_equal(aside, meta["aside"]), "the set-aside points are not the planned ones"
+        shard = -(-len(X) // meta["world"])
+        joined_other = set()
+        for st in steps:
+            bu, bp = st["b"]
+            created = {}
+            for i, u, p in zip(st["deferred"], bu, bp):
+                if p == 2:
+                    created[int(u)] = int(i) // shard
+                elif int(u) in created and created[int(u)] != int(i) // shard:
+                    joined_other.add(int(u))
+        counts = dict(set_aside=res["stats"]["deferred_points"], by_step=[len(st["deferred"]) for st in steps],
+                      created_and_joined_by_other_ranks=len(joined_other))
+        assert counts["set_aside"] == len(meta["aside"])
+        if meta["world"] >= 3:
+            assert len(joined_other) >= 2, counts
+    elif kind == "relaxed-moving":
+        changed, a_to_b = 0, 0
+        pair = dict(zip((int(u) for u in meta["A"]), (int(u) for u in meta["B"])))
+        for s in range(1, len(steps)):
+            before, after = steps[s - 1]["before"]["pcore"], steps[s]["before"]["pcore"]
+            for a, e in steps[s]["ranges"]:
+                nb, na = _nearest(X[a:e], before), _nearest(X[a:e], after)
+                changed += int((nb != na).sum())
+                a_to_b += sum(1 for x, y in zip(nb, na) if pair.get(int(x)) == int(y))
+        counts = dict(merges=len(steps), nearest_row_changed_by_a_merge=changed, from_A_to_B=a_to_b)
+        assert len(steps) >= 8 and changed >= 16, counts
+    elif kind == "relaxed-threshold":
+        on = 0
+        want = set(int(u) for u in meta["uids"])
+        for st in steps:
+            for name in ("pcore", "outlier"):
+                t = st["merged"][name]
+                sel = np.array([int(u) in want for u in t["uid"]], bool)
+                var = t["cf2"][sel, 0] / t["w"][sel] - (t["cf1"][sel, 0] / t["w"][sel]) ** 2
+                hit = (var == par.delta_sq) & (t["w"][sel] == 4.0)
+                assert (t["pref"][sel, 0][hit] == par.k).all()
+                on += int(hit.sum())
+        counts = dict(merged_variances_on_delta_sq=on, rows=len(want))
+        assert on == len(want), counts
+    elif kind == "relaxed-tainted":
+        touched = {}
+        for st in steps:
+            if st["info"] is not None:
+                for u, t in zip(st["info"]["rows"]["uid"], st["info"]["touched"]):
+                    touched[int(u)] = touched.get(int(u), False) or bool(t)
+            for u in st["b"][0]:
+                touched[int(u)] = True
+        final = {int(u): res["state"][name]["pref"][r] for name in ("pcore", "outlier")
+                 for r, u in enumerate(res["state"][name]["uid"])}
+        for name, t in (("pcores", pcores), ("outliers", outliers)):
+            if t is None:
+                continue
+            hit = np.array([touched.get(int(u), False) for u in t.uid])
+            counts[name] = dict(touched=int(hit.sum()), untouched=int((~hit).sum()))
+            for r in np.flatnonzero(~hit):
+                assert np.array_equal(final[int(t.uid[r])].view(np.int64), t.pref[r].view(np.int64)), "an untouched row's entries changed"
+            if meta.get("full", True) or len(t) >= 31:
+                assert hit.any() and not hit.all(), (name, counts)
+    else:
+        raise ValueError(kind)
+    return counts
+
+
+# every case of tests/test_relaxed_model.py and tests/test_relaxed_model_cpu.py: name -> (generator, arguments).  At most 2 148
+# rows and 7 500 points.  Widths: 3 below the ladder, 8, 13 and 37 over padded operands, 20 and 40 on the ladder, 64 the last
+# windowed one.
+RELAXED_DIMS = (3, 8, 13, 20, 37, 40, 64)
+RELAXED_TABLES = {}
+for _d in RELAXED_DIMS:
+    RELAXED_TABLES["divergence-3x100x%d" % _d] = (relaxed_divergence, dict(seed=400 + _d, d=_d))
+    RELAXED_TABLES["tainted-2x150x%d" % _d] = (relaxed_tainted, dict(seed=500 + _d, d=_d))
+    RELAXED_TABLES["victims-3x20x%d" % _d] = (relaxed_victims, dict(seed=600 + _d, d=_d))
+    RELAXED_TABLES["promotions-small-3x200x%d" % _d] = (relaxed_promotions, dict(seed=700 + _d, d=_d, per_rank=200, m_p=20, m_o=210,
+                                                                            minibatch=256))
+    RELAXED_TABLES["threshold-2x64x%d" % _d] = (relaxed_threshold, dict(seed=750 + _d, d=_d))
+for _d in (8, 20):
+    RELAXED_TABLES["promotions-3x2500x%d" % _d] = (relaxed_promotions, dict(seed=800 + _d, d=_d))
+for _d in (8, 13, 37):
+    RELAXED_TABLES["compaction-3x2500x%d" % _d] = (relaxed_compaction, dict(seed=900 + _d, d=_d))
+RELAXED_TABLES["compaction-1x5000x8"] = (relaxed_compaction, dict(seed=950, d=8, world=1, per_rank=5000, first=2048))
+RELAXED_TABLES["compaction-4x1875x20"] = (relaxed_compaction, dict(seed=951, d=20, world=4, per_rank=1875))
+for _d in (20, 40):
+    RELAXED_TABLES["moving-2x2304x%d" % _d] = (relaxed_moving, dict(seed=1000 + _d, d=_d))
+    RELAXED_TABLES["tainted-3x700x%d" % _d] = (relaxed_tainted, dict(seed=1100 + _d, d=_d, world=3, minibatch=256, m_p=1400,
+                                                                    m_o=700, n=2100, filt=_d == 20))
+del _d
+
+
+# the stream of the decay tests: timepoints 0, 1 and 3 with lambda = 0.5 (factors 2^-0.5 and 2^-1: fractional weights), 15 % of
+# the blobs replaced per timepoint, promotion after 40 points and omicron 3 points: retired blobs are downgraded, light outlier
+# microclusters deleted (tests/test_relaxed_model_cpu.py counts them)
+RELAXED_DECAY = dict(seed=31, n=3000, d=14, g=40, sigma=0.01, timepoints=3, drift=0.005, churn=0.15)
+RELAXED_DECAY_DAYS = [0, 1, 3]
+
+
+def relaxed_decay_config():
+    import scenarios
+    return scenarios.params_to_config(scenarios.blob_params(RELAXED_DECAY["n"], promote_after=40, param_lambda=0.5,
+                                                            param_omicron=0.001))
+
+
+def build_relaxed(name):
+    gen, kw = RELAXED_TABLES[name]
+    return gen(**kw)
+
+
 if __name__ == "__main__":  # the structure conditions of every table against the oracle alone (no GPU)
     import os
     import sys

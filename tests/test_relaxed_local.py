@@ -1,6 +1,9 @@
 """The RELAXED multi-GPU mode (events of a timepoint sharded over the ranks, CF deltas all-reduced per super-step;
 cc_comm_set_relaxed) on in-process groups of handles on one GPU.  It is not the reference's algorithm, so nothing here
-is compared bit for bit with the reference; what is pinned:
+is compared bit for bit with the reference.  Per point and per row the mode is refereed elsewhere: tests/test_relaxed_model.py
+compares labels, both lists (id, uid, w, CF1, CF2, centroid, preferred dimensions), the id counters and cc_relaxed_stats of every
+rank bit for bit with tests/relaxed_model.py, a CPU model of DESIGN.md section 6 (3) on the oracle, on injected tables of up to
+2 100 rows.  What is pinned here, on streams of 40 000 to 2 M points:
   - every rank ends every timepoint with bit-identical tables, labels, counters and clusters (the property the
     replicated halves of the super-steps and the offline phase rely on);
   - conservation: every point is labelled, every MC's weight is the number of its points (first timepoint), CF1 is the
