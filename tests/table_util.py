@@ -849,6 +849,9 @@ def check_online(case, res):
             assert (path[tag == "beyond"] == 2).all() and (path[tag == "far"] == 2).all()
             if outliers is not None and len(outliers) >= 64:
                 assert (path == 5).any()
+    elif kind == "arrivals":                                   # designed arrivals: tests/arrival_util.py
+        import arrival_util
+        arrival_util.check_arrivals(case, res)
     else:
         raise ValueError(kind)
 
