@@ -114,6 +114,77 @@ VIEW_DTYPES = {np.dtype(t): code for t, code in (
     (np.int16, DT_I16), (np.uint16, DT_U16), (np.int32, DT_I32), (np.uint32, DT_U32))}
 
 
+class CcListMode(C.Structure):
+    """cc_list_mode: list-mode event records as the bytes an FCS DATA segment holds."""
+    _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("src_cols", C.c_int32), ("dtype", C.c_int32),
+                ("flags", C.c_int32), ("d", C.c_int32), ("cols", C.POINTER(C.c_int32)), ("masks", C.POINTER(C.c_uint32))]
+
+
+LM_SWAPPED = 1
+MAX_SRC_COLS = 4096
+# the element types list-mode data has, by numpy dtype in native byte order
+LIST_DTYPES = {np.dtype(t): code for t, code in (
+    (np.float32, DT_F32), (np.float64, DT_F64), (np.uint8, DT_U8), (np.uint16, DT_U16), (np.uint32, DT_U32))}
+
+
+class ListMode(object):
+    """List-mode event records where they lie (cc_list_mode): `buffer` holds n records of src_cols elements of `dtype` - a
+    numpy dtype WITH its byte order, float32 / float64 / uint8 / uint16 / uint32 -, of which `columns` (indices into the
+    record, any order, repeats allowed; None: all of them) are the dimensions, the integer ones ANDed with `masks` (one per
+    selected column; None: none).  The buffer may start at any address and is kept alive by this object; it is never copied
+    or packed on the host: the `_list` entry points move whole records and the device swaps, gathers, masks and widens.
+    shape == (n, d), ndim == 2; np.asarray(list_mode) is the host decode - float32 for float32 sources, else float64 -, the
+    referee of the device route and the fallback of every host-side consumer."""
+
+    ndim = 2
+
+    def __init__(self, buffer, n, src_cols, dtype, columns=None, masks=None):
+        dtype = np.dtype(dtype)
+        if dtype.newbyteorder("=") not in LIST_DTYPES:
+            raise ValueError("ListMode: dtype %s is none of float32, float64, uint8, uint16, uint32" % dtype)
+        n, src_cols = int(n), int(src_cols)
+        if n < 0 or src_cols < 1:
+            raise ValueError("ListMode: n must be non-negative and src_cols positive")
+        self._bytes = np.frombuffer(buffer, dtype=np.uint8)  # (keeps the buffer alive; any address)
+        if self._bytes.size < n * src_cols * dtype.itemsize:
+            raise ValueError("ListMode: the buffer holds %d bytes, %d records of %d x %s need %d"
+                             % (self._bytes.size, n, src_cols, dtype, n * src_cols * dtype.itemsize))
+        self.buffer = buffer
+        self.n, self.src_cols, self.dtype = n, src_cols, dtype
+        self.swapped = not dtype.isnative
+        self.columns = np.arange(src_cols, dtype=np.int32) if columns is None else np.ascontiguousarray(columns, dtype=np.int32)
+        if self.columns.ndim != 1 or self.columns.size < 1:
+            raise ValueError("ListMode: columns must be a non-empty list of indices")
+        if self.columns.min() < 0 or self.columns.max() >= src_cols:
+            raise ValueError("ListMode: a column is outside 0..%d" % (src_cols - 1))
+        self.masks = None
+        if masks is not None:
+            if dtype.kind != "u":
+                raise ValueError("ListMode: masks are for the integer dtypes only")
+            self.masks = np.ascontiguousarray(masks, dtype=np.uint32)
+            if self.masks.shape != self.columns.shape:
+                raise ValueError("ListMode: one mask per selected column")
+        self.shape = (n, int(self.columns.size))
+
+    def __len__(self):
+        return self.n
+
+    def descriptor(self):
+        """The cc_list_mode of these records (it points into this object: keep it alive while the descriptor is used)."""
+        return CcListMode(self._bytes.ctypes.data if self._bytes.size else None, self.n, self.src_cols,
+                          LIST_DTYPES[self.dtype.newbyteorder("=")], LM_SWAPPED if self.swapped else 0, self.shape[1],
+                          self.columns.ctypes.data_as(C.POINTER(C.c_int32)),
+                          None if self.masks is None else self.masks.ctypes.data_as(C.POINTER(C.c_uint32)))
+
+    def __array__(self, dtype=None, copy=None):
+        rec = np.frombuffer(self._bytes, dtype=self.dtype, count=self.n * self.src_cols).reshape(self.n, self.src_cols)
+        out = rec[:, self.columns]
+        if self.masks is not None:
+            out = out.astype(self.dtype.newbyteorder("=")) & self.masks.astype(self.dtype.newbyteorder("="))
+        out = out.astype(np.float32 if self.dtype.itemsize == 4 and self.dtype.kind == "f" else np.float64)
+        return out if dtype is None else out.astype(dtype, copy=False)
+
+
 class CcRelaxedStats(C.Structure):
     _fields_ = [("super_steps", C.c_int64), ("minibatch_points", C.c_int64), ("deferred_points", C.c_int64),
                 ("reserved", C.c_int64 * 5)]
@@ -125,6 +196,7 @@ _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
 _i8p = C.POINTER(C.c_int8)
 _vp = C.POINTER(CcPointsView)
+_lp = C.POINTER(CcListMode)
 
 # name -> (restype, argtypes): every symbol include/chronoclust_hip.h declares
 SYMBOLS = {
@@ -158,6 +230,12 @@ SYMBOLS = {
     "cc_online_view": (C.c_int, [C.c_void_p, _vp, _i64p, _i8p]),
     "cc_assign_view": (C.c_int, [C.c_void_p, _vp, _i64p, _i8p, _dp]),
     "cc_view_points": (C.c_int, [C.c_void_p, _i64p]),
+    "cc_points_upload_list": (C.c_int, [C.c_void_p, _lp, _dp, _dp]),
+    "cc_points_prefetch_list": (C.c_int, [C.c_void_p, _lp, _dp, _dp]),
+    "cc_col_minmax_list": (C.c_int, [C.c_void_p, _lp, _dp, _dp]),
+    "cc_online_list": (C.c_int, [C.c_void_p, _lp, _i64p, _i8p]),
+    "cc_assign_list": (C.c_int, [C.c_void_p, _lp, _i64p, _i8p, _dp]),
+    "cc_list_points": (C.c_int, [C.c_void_p, _i64p]),
     "cc_count": (C.c_int, [C.c_void_p, C.c_int]),
     "cc_dim": (C.c_int, [C.c_void_p]),
     "cc_counters": (C.c_int, [C.c_void_p, _i64p, _i64p]),
@@ -493,6 +571,8 @@ class Handle(object):
         self._check(self._lib.cc_decay_downgrade(self._h, float(factor)))
 
     def points_upload(self, x):
+        if isinstance(x, ListMode):
+            return self._upload_list(x, None, None)
         x, view = points_source(x)
         if x.ndim != 2:
             raise ValueError("points must be a 2-d array")
@@ -507,6 +587,15 @@ class Handle(object):
             self._prefetched = None  # adopted or discarded by the library: the array is no longer pinned by us
         self._n = x.shape[0]
 
+    def _upload_list(self, lm, scale, min_):
+        """cc_points_upload_list of a ListMode, plain or scaled."""
+        desc = lm.descriptor()
+        try:
+            self._check(self._lib.cc_points_upload_list(self._h, C.byref(desc), _ptr(scale), _ptr(min_)))
+        finally:
+            self._prefetched = None
+        self._n = lm.shape[0]
+
     def points_prefetch(self, x, scale=None, min_=None):
         """Starts the background upload of the NEXT timepoint's points (cc_points_prefetch).  `x` must be the very
         array (C-contiguous float64 or float32, or one points_view accepts) that is later passed to points_upload /
@@ -514,6 +603,15 @@ class Handle(object):
         written to between this call and that upload - the upload is recognised by pointer, shape, layout, element type and
         scaling, and the copy already on the device is used as it is."""
         if isinstance(x, np.ndarray) and x.ndim == 2 and x.shape[0] == 0:
+            return
+        if isinstance(x, ListMode):
+            if x.shape[0] == 0:
+                return
+            scale = None if scale is None else _f64(scale)
+            min_ = None if min_ is None else _f64(min_)
+            self._prefetched = (x, scale, min_)
+            desc = x.descriptor()
+            self._check(self._lib.cc_points_prefetch_list(self._h, C.byref(desc), _ptr(scale), _ptr(min_)))
             return
         src, view = points_source(x)
         if src is not x or x.ndim != 2:
@@ -531,6 +629,12 @@ class Handle(object):
 
     def col_minmax(self, x):
         """Per-column (min, max) of x, NaN ignored, reduced on the device."""
+        if isinstance(x, ListMode):
+            mn = np.empty(x.shape[1], dtype=np.float64)
+            mx = np.empty(x.shape[1], dtype=np.float64)
+            desc = x.descriptor()
+            self._check(self._lib.cc_col_minmax_list(self._h, C.byref(desc), _ptr(mn), _ptr(mx)))
+            return mn, mx
         x, view = points_source(x)
         mn = np.empty(x.shape[1], dtype=np.float64)
         mx = np.empty(x.shape[1], dtype=np.float64)
@@ -544,6 +648,11 @@ class Handle(object):
 
     def points_upload_scaled(self, x, scale, min_):
         """points_upload of x * scale + min_ (MinMaxScaler.transform), scaled on the device."""
+        if isinstance(x, ListMode):
+            scale, min_ = _f64(scale), _f64(min_)
+            if scale.shape != (x.shape[1],) or min_.shape != (x.shape[1],):
+                raise ValueError("points must be [n, d], scale and min_ [d]")
+            return self._upload_list(x, scale, min_)
         (x, view), scale, min_ = points_source(x), _f64(scale), _f64(min_)
         if x.ndim != 2 or scale.shape != (x.shape[1],) or min_.shape != (x.shape[1],):
             raise ValueError("points must be [n, d], scale and min_ [d]")
@@ -595,14 +704,19 @@ class Handle(object):
         the table as it stands - (uid, path, dist): the creation number of the microcluster it would join (-1: it would
         create one), 0 pcore / 1 outlier / 5 outlier that the add promotes / 2 new, the projected distance to that
         microcluster (-1.0 for path 2); path and dist are None unless wanted.  Nothing of the handle changes."""
-        x, view = points_source(x)
+        lm = x if isinstance(x, ListMode) else None
+        if lm is None:
+            x, view = points_source(x)
         if x.ndim != 2:
             raise ValueError("points must be a 2-d array")
         n = x.shape[0]
         uid = np.empty(n, dtype=np.int64)
         path = np.empty(n, dtype=np.int8) if want_path else None
         dist = np.empty(n, dtype=np.float64) if want_dist else None
-        if view is not None:
+        if lm is not None:
+            desc = lm.descriptor()
+            self._check(self._lib.cc_assign_list(self._h, C.byref(desc), _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
+        elif view is not None:
             self._check(self._lib.cc_assign_view(self._h, C.byref(view), _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
         elif x.dtype == np.float32:
             self._check(self._lib.cc_assign_f32(self._h, _ptr(x, _fp), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
@@ -743,6 +857,7 @@ class Handle(object):
         out = {k: getattr(s, k) for k, _ in CcStats._fields_ if k != "reserved"}
         out["f32_points"] = self.f32_points()
         out["view_points"] = self.view_points()
+        out["list_points"] = self.list_points()
         return out
 
     def f32_points(self):
@@ -750,6 +865,13 @@ class Handle(object):
         prefetches and assigns of float32 arrays.  stats() carries it as "f32_points" beside the fields of cc_stats."""
         n = C.c_int64()
         self._check(self._lib.cc_f32_points(self._h, C.byref(n)))
+        return n.value
+
+    def list_points(self):
+        """Events this handle has taken through the `_list` entry points since it was created (cc_list_points): uploads,
+        adopted prefetches and assigns of ListMode records.  stats() carries it as "list_points"."""
+        n = C.c_int64()
+        self._check(self._lib.cc_list_points(self._h, C.byref(n)))
         return n.value
 
     def view_points(self):

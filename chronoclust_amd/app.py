@@ -189,6 +189,8 @@ def write_datapoints_details(dataset_attributes, clusters, hddstream, raw, clust
     if scaler:
         # the reference writes inverse_transform(transform(raw)), not raw: (X - min_) / scale_ on the device
         values = hddstream.resident_points(scaler.scale_, scaler.min_)
+    elif isinstance(raw, _lib.ListMode):
+        values = hddstream.resident_points()  # (event records decoded on the device: read back, as under scaling)
     else:
         values = raw
     usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -290,6 +292,10 @@ def append_to_file(filename, content):
 
 
 def get_dataset_attributes(dataset_file):
+    if str(dataset_file).lower().endswith(".fcs"):
+        # the channels `<file>.columns` names (as it names them), else every channel's $PnN in file order
+        from .fcs import read_fcs, sidecar_columns
+        return sidecar_columns(dataset_file) or read_fcs(dataset_file)[1]
     if str(dataset_file).endswith(".npy"):
         # binary side input: column names from `<file>.columns` (one name per line) if present
         names_file = str(dataset_file) + ".columns"

@@ -3,7 +3,8 @@
 // kernels of cc_online.h / cc_offline.h on its HIP streams.  No CPU fallback exists for any kernel.
 // Here: the snapshot scan's plan and dispatcher, the handle's life cycle and settings, the online and table entry points.
 // Beside it, included below: cc_handle.h (the handle, its buffers and helpers; cc_knobs.h), cc_online_run.h (one online
-// call), cc_api_points.inc, cc_api_offline.inc, cc_api_comm.inc and cc_api_assign.inc (the other entry points, by concern).
+// call), cc_api_points.inc, cc_api_views.inc, cc_api_list.inc, cc_api_offline.inc, cc_api_comm.inc and cc_api_assign.inc (the other
+// entry points, by concern).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -383,11 +384,13 @@ Rows padded_rows(cc_handle* h, hipStream_t st, Rows rows, int q, int round, int 
 
 }  // namespace
 
-// one online call (OnlineRun, online_range), then the entry points by concern: points, point views, offline phase and tracker, multi-GPU,
+// one online call (OnlineRun, online_range), then the entry points by concern: points, point views, list-mode records, offline phase and
+// tracker, multi-GPU,
 // read-only assignment
 #include "cc_online_run.h"
 #include "cc_api_points.inc"
 #include "cc_api_views.inc"
+#include "cc_api_list.inc"
 #include "cc_api_offline.inc"
 #include "cc_api_comm.inc"
 #include "cc_api_assign.inc"

@@ -6,7 +6,8 @@
 // on a handle of a group the rank's own table is read.  cc_assign_f32: the same chunks, each uploaded in single precision into
 // the set's raw buffer and taken in by k_ingest_f32 (cc_points.h) instead of the check and the transpose.
 // cc_assign_view: the same chunks again, each staged as the view lies (view_stage, cc_api_views.inc) in sub-slabs of at most
-// 16 MiB through the set's raw buffer and taken in by k_ingest.
+// 16 MiB through the set's raw buffer and taken in by k_ingest.  cc_assign_list: the same chunks once more, whole event records in
+// sub-slabs of at most 16 MiB through the set's raw buffer and taken in by k_ingest_list (cc_api_list.inc).
 // (included by cc_api.hip, the one translation unit, behind cc_handle.h)
 
 namespace {
@@ -31,12 +32,13 @@ int assign_segments(const cc_handle* h, int64_t chunk, int m_rows)
     return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, most), 64));
 }
 
-// vs: the points are this view (cc_assign_view; x and f32 are then unused)
-int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, int64_t n, int d, int64_t* out_uid, int8_t* out_path,
+// vs: the points are this view (cc_assign_view; x and f32 are then unused); ls: these event records (cc_assign_list; likewise)
+int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, const ListSrc* ls, int64_t n, int d, int64_t* out_uid, int8_t* out_path,
                double* out_dist, bool* nonfinite)
 {
     if (f32) h->f32_points += n;
     if (vs) h->view_points += n;
+    if (ls) h->list_points += n;
     h->stats.assign_points = n;
     h->stats.assign_launches = 0;
     if (n == 0) return (int)CC_OK;
@@ -53,16 +55,23 @@ int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, int64_t
     hipStream_t st[2] = {h->stream, h->stream2};
     const int sets = n > chunk ? 2 : 1;
     // a view's chunk goes through the set's raw buffer in sub-slabs of at most 16 MiB of staging, whatever the view's pitch
-    const int64_t sub = vs ? std::min<int64_t>(view_slab_points(h, *vs, (size_t)16 << 20), (chunk + 63) & ~(int64_t)63) : 0;
+    const int64_t sub = vs ? std::min<int64_t>(view_slab_points(h, *vs, (size_t)16 << 20), (chunk + 63) & ~(int64_t)63)
+                      : ls ? std::min<int64_t>(list_slab_points(h, *ls, (size_t)16 << 20), (chunk + 63) & ~(int64_t)63) : 0;
     for (int q = 0; q < sets; ++q) {
         AssignBuffers::Set& b = h->asg[q];
         b.X.ensure((size_t)chunk * d); b.Xt.ensure((size_t)chunk * d);
         if (f32) b.raw.ensure((size_t)chunk * d);
         if (vs) b.raw.ensure(view_slab_floats(*vs, sub));
+        if (ls) b.raw.ensure(list_slab_floats(*ls, sub));
         b.uid.ensure((size_t)chunk); b.path.ensure((size_t)chunk); b.dist.ensure((size_t)chunk);
         b.part.ensure((size_t)chunk * S * 2);
         b.bad.ensure(4);
         HIPCHK(hipMemsetAsync(b.bad.p, 0, 16, st[q]));
+    }
+    if (ls) {
+        // the descriptors once, for both streams
+        list_desc_upload(h->stream, *ls, h->list_desc);
+        sync_stream(h, h->stream);
     }
     std::vector<char> pack;
     int64_t off = 0;
@@ -79,6 +88,12 @@ int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, int64_t
                 view_stage(st[q], *vs, off + s0, ns, b.raw.p, pack);
                 ingest_view_launch(st[q], b.raw.p, vs->dtype, vs->cols, vs->pitch(ns), ns, s0, cn, d, (size_t)d, b.X.p, b.Xt.p,
                                    nullptr, nullptr, b.bad.p);
+            }
+        } else if (ls) {
+            for (int64_t s0 = 0; s0 < cn; s0 += sub) {
+                const int64_t ns = std::min<int64_t>(sub, cn - s0);
+                HIPCHK(hipMemcpyAsync(b.raw.p, ls->at(off + s0), (size_t)ns * ls->record_bytes(), hipMemcpyHostToDevice, st[q]));
+                ingest_list_launch(st[q], b.raw.p, *ls, h->list_desc.p, ns, s0, cn, (size_t)d, b.X.p, b.Xt.p, nullptr, nullptr, b.bad.p);
             }
         } else if (f32) {
             HIPCHK(hipMemcpyAsync(b.raw.p, static_cast<const float*>(x) + (size_t)off * d, (size_t)tot * 4, hipMemcpyHostToDevice, st[q]));
@@ -114,7 +129,7 @@ int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, int64_t
     return (int)CC_OK;
 }
 
-int assign_points(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
+int assign_points(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, const ListSrc* ls, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
                   double* out_dist)
 {
     if (!h || n < 0 || (n > 0 && (!x || !out_uid))) return CC_ERR_BAD_ARG;
@@ -122,7 +137,7 @@ int assign_points(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, int6
     if (d <= 0 || d > CC_MAX_DIM) return fail(h, CC_ERR_BAD_ARG, "d must be in 1.." + std::to_string(CC_MAX_DIM));
     if (h->hc.m_rows > 0 && d != h->d) return fail(h, CC_ERR_BAD_ARG, "dimensionality differs from the microclusters already held");
     bool nonfinite = false;
-    const int rc = guarded(h, [&]() { return assign_run(h, x, f32, vs, n, d, out_uid, out_path, out_dist, &nonfinite); });
+    const int rc = guarded(h, [&]() { return assign_run(h, x, f32, vs, ls, n, d, out_uid, out_path, out_dist, &nonfinite); });
     // (outside guarded: a refused query is no reason to give up the handle's group)
     if (rc == CC_OK && nonfinite) return fail(h, CC_ERR_NONFINITE, "input points contain NaN or Inf");
     return rc;
@@ -133,13 +148,13 @@ int assign_points(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, int6
 extern "C" int cc_assign(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
                          double* out_dist)
 {
-    return assign_points(h, x, false, nullptr, n, d, out_uid, out_path, out_dist);
+    return assign_points(h, x, false, nullptr, nullptr, n, d, out_uid, out_path, out_dist);
 }
 
 extern "C" int cc_assign_f32(cc_handle* h, const float* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
                              double* out_dist)
 {
-    return assign_points(h, x, true, nullptr, n, d, out_uid, out_path, out_dist);
+    return assign_points(h, x, true, nullptr, nullptr, n, d, out_uid, out_path, out_dist);
 }
 
 extern "C" int cc_assign_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path, double* out_dist)
@@ -147,5 +162,13 @@ extern "C" int cc_assign_view(cc_handle* h, const cc_points_view* view, int64_t*
     ViewSrc v;
     const int rc = view_check(h, view, false, &v);
     if (rc != CC_OK) return rc;
-    return assign_points(h, v.data, false, &v, v.n, v.d, out_uid, out_path, out_dist);
+    return assign_points(h, v.data, false, &v, nullptr, v.n, v.d, out_uid, out_path, out_dist);
+}
+
+extern "C" int cc_assign_list(cc_handle* h, const cc_list_mode* lm, int64_t* out_uid, int8_t* out_path, double* out_dist)
+{
+    ListSrc v;
+    const int rc = list_check(h, lm, false, &v);
+    if (rc != CC_OK) return rc;
+    return assign_points(h, v.data, false, nullptr, &v, v.n, v.d, out_uid, out_path, out_dist);
 }

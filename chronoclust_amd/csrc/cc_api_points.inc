@@ -136,7 +136,7 @@ static int upload_points(cc_handle* h, const void* x, bool f32, int64_t n, int32
     if (h->pf.active) {
         // the points may already be on their way (cc_points_prefetch): adopt them if it is this very upload
         cc_handle::Prefetch& pf = h->pf;
-        bool same = !pf.view && pf.x == x && pf.f32 == f32 && pf.n == n && pf.d == d && pf.scaled == (scale != nullptr);
+        bool same = !pf.view && !pf.list && pf.x == x && pf.f32 == f32 && pf.n == n && pf.d == d && pf.scaled == (scale != nullptr);
         for (int i = 0; same && scale && i < d; ++i) same = pf.scale[i] == scale[i] && pf.mn[i] == mn[i];
         const bool ok = prefetch_join(h);
         pf.active = false;
@@ -215,7 +215,7 @@ static int points_prefetch(cc_handle* h, const void* x, bool f32, int64_t n, int
     return guarded(h, [&]() {
         prefetch_discard(h);
         cc_handle::Prefetch& pf = h->pf;
-        pf.x = x; pf.f32 = f32; pf.view = false; pf.n = n; pf.d = d; pf.scaled = scale != nullptr;
+        pf.x = x; pf.f32 = f32; pf.view = false; pf.list = false; pf.n = n; pf.d = d; pf.scaled = scale != nullptr;
         pf.scale.assign(scale, scale ? scale + d : scale);
         pf.mn.assign(min_, min_ ? min_ + d : min_);
         pf.rc = 0; pf.what = ""; pf.bad_host[0] = pf.bad_host[1] = pf.bad_host[2] = pf.bad_host[3] = 0;

@@ -257,7 +257,7 @@ int prefetch_view(cc_handle* h, const ViewSrc& v, const double* scale, const dou
     cc_handle::Prefetch& pf = h->pf;
     const int64_t n = v.n;
     const int d = v.d;
-    pf.x = v.data; pf.f32 = false; pf.view = true; pf.dtype = v.dtype; pf.rs = v.rs; pf.cs = v.cs;
+    pf.x = v.data; pf.f32 = false; pf.view = true; pf.list = false; pf.dtype = v.dtype; pf.rs = v.rs; pf.cs = v.cs;
     pf.n = n; pf.d = d; pf.scaled = scale != nullptr;
     pf.scale.assign(scale, scale ? scale + d : scale);
     pf.mn.assign(min_, min_ ? min_ + d : min_);

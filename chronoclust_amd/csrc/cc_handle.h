@@ -322,6 +322,8 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
     DevBuf<float> ingest_raw[2];  // cc_points_upload_f32: the two slabs of raw single-precision points (k_ingest_f32 reads them)
     long long f32_points = 0;     // cc_f32_points: points taken in single precision since cc_create
     long long view_points = 0;    // cc_view_points: points taken through the `_view` entry points since cc_create (they share ingest_raw, in bytes)
+    long long list_points = 0;    // cc_list_points: events taken through the `_list` entry points since cc_create (ingest_raw again)
+    DevBuf<int> list_desc;        // ... their descriptors {source column, mask} on the device, uploaded once per call (k_ingest_list)
 
     // cc_points_prefetch: the next timepoint's points, uploaded by a worker thread through page-locked staging
     struct Prefetch {
@@ -336,6 +338,10 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
         bool view = false;              // x is element (0, 0) of a cc_points_view of this dtype and these strides (k_ingest; pieces as for f32)
         int dtype = 0;
         long long rs = 0, cs = 0;
+        bool list = false;              // x is event 0 of a cc_list_mode of this dtype, these flags, src_cols and descriptors (k_ingest_list; pieces as for f32)
+        int src_cols = 0, flags = 0;
+        std::vector<cc_list_desc> ldesc;
+        DevBuf<int> desc;               // ... the descriptors on the device
         DevBuf<float> raw[2];
         std::vector<double> scale, mn;
         DevBuf<double> X, Xt, sm;       // destination buffers (swapped with the handle's on adoption), scale / min

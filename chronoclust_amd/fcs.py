@@ -1,0 +1,226 @@
+"""Flow Cytometry Standard files (FCS 2.0 / 3.0 / 3.1, list mode) read where they lie.
+
+read_fcs memory-maps the file, parses HEADER and TEXT and hands the DATA segment out as a `_lib.ListMode` - the bytes the
+file holds, in the file's byte order, every channel of an event interleaved - which Handle.points_upload and its kin move to
+the device as they are: the byte swap, the selection of the channels, the `$PnR` range mask and the widening happen there
+(cc_points_upload_list).  Layouts the device route does not take are decoded on the host into a float64 array."""
+import numpy as np
+
+from ._lib import ListMode
+
+VERSIONS = (b"FCS2.0", b"FCS3.0", b"FCS3.1")
+
+
+def _header_offsets(head):
+    """The six offsets of the HEADER: TEXT, DATA, ANALYSIS begin / end (end offsets inclusive; blank = 0)."""
+    if len(head) < 58:
+        raise ValueError("FCS HEADER: the file is shorter than the 58 bytes of a header")
+    if head[:6] not in VERSIONS:
+        raise ValueError("FCS HEADER: version %r is none of FCS2.0, FCS3.0, FCS3.1" % head[:6])
+    out = []
+    for i in range(6):
+        field = head[10 + 8 * i:18 + 8 * i].strip()
+        try:
+            out.append(int(field) if field else 0)
+        except ValueError:
+            raise ValueError("FCS HEADER: offset %d is %r, not a number" % (i, field)) from None
+        if out[-1] < 0:
+            raise ValueError("FCS HEADER: offset %d is negative" % i)
+    return out
+
+
+def parse_text(segment):
+    """The TEXT segment as a dict, keywords upper-cased: the first byte is the delimiter, keywords and values alternate, a
+    doubled delimiter inside a keyword or value is a literal one (so no value is empty)."""
+    if len(segment) < 2:
+        raise ValueError("FCS TEXT: the segment is empty")
+    delim = segment[0:1]
+    tokens, cur, i, n = [], bytearray(), 1, len(segment)
+    while i < n:
+        c = segment[i:i + 1]
+        if c == delim:
+            if segment[i + 1:i + 2] == delim:
+                cur += delim
+                i += 2
+                continue
+            tokens.append(bytes(cur))
+            cur = bytearray()
+        else:
+            cur += c
+        i += 1
+    if cur.strip(b" \x00\r\n"):
+        tokens.append(bytes(cur))  # (a last value without its closing delimiter)
+    if len(tokens) % 2:
+        raise ValueError("FCS TEXT: keyword %r has no value" % tokens[-1].decode("latin-1"))
+    text = {}
+    for k, v in zip(tokens[0::2], tokens[1::2]):
+        text[k.decode("latin-1").strip().upper()] = v.decode("latin-1")
+    return text
+
+
+def _need(text, key):
+    if key not in text:
+        raise ValueError("FCS TEXT: %s is missing" % key)
+    return text[key].strip()
+
+
+def _int(text, key):
+    val = _need(text, key)
+    try:
+        return int(val)
+    except ValueError:
+        try:
+            f = float(val)
+            if f == int(f):
+                return int(f)
+        except ValueError:
+            pass
+        raise ValueError("FCS TEXT: %s is %r, not an integer" % (key, val)) from None
+
+
+def range_mask(pnr, bits):
+    """The AND mask of an integer channel of `bits` bits whose $PnR is pnr: 2^ceil(log2(pnr)) - 1 where that is below the
+    all-ones of the channel's width, else None."""
+    m = (1 << max(int(pnr) - 1, 0).bit_length()) - 1
+    return m if m < (1 << bits) - 1 else None
+
+
+def _select(columns, names, stains):
+    if columns is None:
+        return list(range(len(names)))
+    out = []
+    for c in columns:
+        if isinstance(c, (int, np.integer)):
+            if not 0 <= int(c) < len(names):
+                raise ValueError("FCS: column index %d is outside 0..%d" % (c, len(names) - 1))
+            out.append(int(c))
+        elif c in names:
+            out.append(names.index(c))
+        elif c in stains:
+            out.append(stains.index(c))
+        else:
+            raise ValueError("FCS: no channel whose $PnN or $PnS is %r (channels: %s)" % (c, ", ".join(names)))
+    if not out:
+        raise ValueError("FCS: the column list is empty")
+    return out
+
+
+def _host_decode(raw, tot, par, datatype, widths, order, masks):
+    """[tot, par] float64 of a list-mode layout the device route does not take: channel widths that differ or are no 8, 16 or
+    32 bits (whole bytes up to 64 bits), byte orders that are a permutation of the element's bytes."""
+    ascending, descending = order == sorted(order), order == sorted(order, reverse=True)
+    nbytes = [w // 8 for w in widths]
+    rec = np.frombuffer(raw, dtype=np.uint8, count=tot * sum(nbytes)).reshape(tot, sum(nbytes))
+    out = np.empty((tot, par), np.float64)
+    at = 0
+    for c, nb in enumerate(nbytes):
+        field = rec[:, at:at + nb]
+        at += nb
+        if ascending or descending:
+            sig = list(range(nb)) if ascending else list(range(nb - 1, -1, -1))
+        elif len(order) == nb:
+            sig = [o - 1 for o in order]
+        else:
+            raise ValueError("FCS TEXT: $BYTEORD %s does not describe an element of %d bytes ($P%dB)"
+                             % (",".join(map(str, order)), nb, c + 1))
+        le = np.zeros((tot, 8), np.uint8)  # the element's bytes, least significant first
+        for i, s in enumerate(sig):
+            le[:, s] = field[:, i]
+        if datatype == "I":
+            val = le.view("<u8")[:, 0]
+            out[:, c] = (val if masks[c] is None else val & np.uint64(masks[c])).astype(np.float64)
+        elif nb == 4:
+            out[:, c] = np.ascontiguousarray(le[:, :4]).view("<f4")[:, 0]
+        else:
+            out[:, c] = le.view("<f8")[:, 0]
+    return out
+
+
+def read_fcs(path, columns=None):
+    """(points, names, text) of a list-mode FCS file.
+
+    points: the DATA segment as a `_lib.ListMode` over the memory-mapped file - nothing is decoded or copied on the host -
+    when $DATATYPE is F (32 bits) or D (64 bits), or I with every $PnB equal and 8, 16 or 32, $BYTEORD is 1,2,3,4 or 4,3,2,1
+    (or 1,2 / 2,1) and the segment holds at least $TOT * $PAR elements.  For I the mask of a channel is
+    2^ceil(log2($PnR)) - 1 where that is below the all-ones of $PnB bits.  Any other list-mode layout - $PnB that differ,
+    24 / 40 / 48 / 56 / 64-bit integers, byte orders such as 3,4,1,2 - comes back decoded on the host as a float64 ndarray
+    [n, d], which takes the routes an ndarray has always taken.
+    columns: the channels to take, in this order - names matched against $PnN, then $PnS, or indices; None: all, in file order.
+    names: the $PnN of the channels taken.  text: the TEXT segment's keywords (upper-cased) and values.
+    The values are the channel values AS STORED: the amplification keywords $PnE (logarithmic decades) and $PnG (linear gain)
+    are NOT applied.
+    ValueError naming the keyword for: $DATATYPE A, a $MODE other than L, a DATA segment shorter than $TOT * $PAR elements,
+    channel widths that are no whole bytes, a malformed HEADER or TEXT."""
+    mm = np.memmap(path, dtype=np.uint8, mode="c")  # (copy-on-write: the pages are the file's until somebody writes, nobody does)
+    size = mm.size
+    text_lo, text_hi, data_lo, data_hi = _header_offsets(bytes(mm[:58]))[:4]
+    if not 58 <= text_lo <= text_hi < size:
+        raise ValueError("FCS HEADER: the TEXT offsets %d..%d lie outside the file (%d bytes)" % (text_lo, text_hi, size))
+    text = parse_text(bytes(mm[text_lo:text_hi + 1]))
+    if data_lo == 0 and data_hi == 0:  # (files beyond 99 999 999 bytes: the header's fields are too narrow)
+        data_lo, data_hi = _int(text, "$BEGINDATA"), _int(text, "$ENDDATA")
+    mode = _need(text, "$MODE").upper()
+    if mode != "L":
+        raise ValueError("FCS TEXT: $MODE %s is not list mode (L)" % mode)
+    datatype = _need(text, "$DATATYPE").upper()
+    if datatype not in ("I", "F", "D"):
+        raise ValueError("FCS TEXT: $DATATYPE %s is not taken (I, F and D are)" % datatype)
+    par = _int(text, "$PAR")
+    if par < 1:
+        raise ValueError("FCS TEXT: $PAR is %d" % par)
+    byteord = _need(text, "$BYTEORD")
+    try:
+        order = [int(v) for v in byteord.split(",")]
+    except ValueError:
+        raise ValueError("FCS TEXT: $BYTEORD is %r" % byteord) from None
+    if sorted(order) != list(range(1, len(order) + 1)):
+        raise ValueError("FCS TEXT: $BYTEORD %s is no permutation of 1..%d" % (text["$BYTEORD"], len(order)))
+    widths = [_int(text, "$P%dB" % (i + 1)) for i in range(par)]
+    names = [text.get("$P%dN" % (i + 1), "P%d" % (i + 1)).strip() for i in range(par)]
+    stains = [text.get("$P%dS" % (i + 1), "").strip() for i in range(par)]
+    if datatype in ("F", "D"):
+        want = 32 if datatype == "F" else 64
+        for i, w in enumerate(widths):
+            if w != want:
+                raise ValueError("FCS TEXT: $P%dB is %d with $DATATYPE %s (%d bits)" % (i + 1, w, datatype, want))
+    for i, w in enumerate(widths):
+        if w % 8 or not 8 <= w <= 64:
+            raise ValueError("FCS TEXT: $P%dB is %d: channels of whole bytes up to 64 bits are taken" % (i + 1, w))
+    event_bytes = sum(widths) // 8
+    if not 0 < data_lo <= data_hi < size:
+        if not (data_lo == 0 and data_hi == 0 and "$TOT" in text and _int(text, "$TOT") == 0):
+            raise ValueError("FCS HEADER: the DATA offsets %d..%d ($BEGINDATA / $ENDDATA) lie outside the file (%d bytes)"
+                             % (data_lo, data_hi, size))
+    held = (data_hi - data_lo + 1) // event_bytes if data_hi else 0
+    tot = _int(text, "$TOT") if "$TOT" in text else held  # (FCS 2.0 may omit it: what the segment holds)
+    if tot < 0 or tot > held:
+        raise ValueError("FCS TEXT: $TOT %d x $PAR %d elements need %d bytes, the DATA segment %d..%d holds %d"
+                         % (tot, par, tot * event_bytes, data_lo, data_hi, data_hi - data_lo + 1 if data_hi else 0))
+    sel = _select(columns, names, stains)
+    picked = [names[c] for c in sel]
+    raw = mm[data_lo:data_lo + tot * event_bytes]
+    ascending, descending = order == sorted(order), order == sorted(order, reverse=True)
+    uniform = len(set(widths)) == 1 and widths[0] in ((32,) if datatype == "F" else (64,) if datatype == "D" else (8, 16, 32))
+    if uniform and (ascending or descending):
+        kind = {"F": "f4", "D": "f8"}.get(datatype) or "u%d" % (widths[0] // 8)
+        dtype = np.dtype(("<" if ascending else ">") + kind)
+        masks = None
+        if datatype == "I":
+            got = [range_mask(_int(text, "$P%dR" % (c + 1)), widths[0]) for c in sel]
+            if any(m is not None for m in got):
+                masks = [0xFFFFFFFF if m is None else m for m in got]
+        return ListMode(raw, tot, par, dtype, columns=sel, masks=masks), picked, text
+    # the layouts of old, on the host
+    masks = [range_mask(_int(text, "$P%dR" % (c + 1)), widths[c]) if datatype == "I" else None for c in range(par)]
+    out = _host_decode(raw, tot, par, datatype, widths, order, masks)
+    return np.ascontiguousarray(out[:, sel]), picked, text
+
+
+def sidecar_columns(path):
+    """The names in `<file>.columns` (one per line, the `.npy` convention), or None without that file."""
+    import os
+    names_file = str(path) + ".columns"
+    if not os.path.exists(names_file):
+        return None
+    with open(names_file) as f:
+        return [line.strip() for line in f if line.strip()]

@@ -8,13 +8,19 @@ tests/test_host_logic.py checks bit equality against scikit-learn."""
 import numpy as np
 import pandas as pd
 
-from .._lib import points_source
+from .._lib import ListMode, points_source
 
 
 def read_timepoint(filename):
     """One timepoint as float64 [N, d].  CSV with a header row as in the reference (app.py:170, scaler.py:31);
     `.npy` files (binary side input: no text parse) are taken as they are - a float32 file stays float32 (cytometry events are
-    single precision at the source; the device widens them), anything else becomes float64."""
+    single precision at the source; the device widens them), anything else becomes float64.  `.fcs` files (fcs.read_fcs) come
+    back as a `_lib.ListMode` over the memory-mapped DATA segment - the device decodes it - or, for the layouts that route
+    does not take, as a float64 array decoded on the host; `<file>.columns` (one name per line, matched against $PnN, then
+    $PnS) selects and orders the channels, without it all channels are taken in file order."""
+    if str(filename).lower().endswith(".fcs"):
+        from ..fcs import read_fcs, sidecar_columns
+        return read_fcs(filename, columns=sidecar_columns(filename))[0]
     if str(filename).endswith(".npy"):
         X = np.load(filename)
         return np.ascontiguousarray(X, dtype=np.float32 if X.dtype == np.float32 else np.float64)
@@ -35,7 +41,9 @@ class Scaler(object):
             for filename in data_files:
                 # (kept as parsed where the library reads it where it lies - pandas hands a CSV out column-major -, else as
                 # a C-contiguous float64 copy)
-                X = points_source(read_timepoint(filename))[0]
+                X = read_timepoint(filename)
+                if not isinstance(X, ListMode):  # (event records of an FCS file: the handle reads them where they lie)
+                    X = points_source(X)[0]
                 self.parsed[filename] = X
                 if X.shape[0] == 0:
                     continue
@@ -46,7 +54,7 @@ class Scaler(object):
         elif data_files is not None:
             rows = []
             for filename in data_files:
-                rows.append(read_timepoint(filename))
+                rows.append(np.asarray(read_timepoint(filename)))
             self.fit_scaler(np.concatenate(rows, axis=0) if rows else np.empty((0, 0)))
 
     def _finish_fit(self, data_min, data_max):

@@ -14,7 +14,9 @@
  *  - host pointers unless the name says "device"; row-major float64 [N, d]
  *    (the `_f32` entry points: row-major float32 [N, d], widened on the device;
  *    the `_view` entry points: a cc_points_view - rows or columns, nine element
- *    types -, widened on the device);
+ *    types -, widened on the device; the `_list` entry points: a cc_list_mode -
+ *    list-mode event records as an FCS file holds them, either byte order, a
+ *    list of channels -, decoded on the device);
  *  - one handle = one HDDStream state on one GPU; a handle is not thread-safe;
  *  - all floating-point work is IEEE double, no FMA contraction, sums over
  *    dimensions strictly left to right, so results are bit-identical to the
@@ -285,6 +287,54 @@ int cc_col_minmax_view(cc_handle* h, const cc_points_view* view, double* out_min
 int cc_online_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path);
 int cc_assign_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path, double* out_dist);
 int cc_view_points(cc_handle* h, int64_t* out);
+
+/* List-mode event records: the DATA segment of a list-mode FCS file as the bytes it holds.  An event is a record of src_cols
+ * elements of one type, in the host's byte order or the other one; the dimensions to cluster on are a LIST of the record's
+ * columns (Time, scatter and marker channels are interleaved: a list, not a range, so no cc_points_view describes them). */
+#define CC_MAX_SRC_COLS 4096
+enum { CC_LM_SWAPPED = 1 };      /* elements are in the other byte order than the host's */
+typedef struct cc_list_mode {
+    const void* data;       /* first byte of event 0; NO alignment is required */
+    int64_t n;              /* events */
+    int32_t src_cols;       /* elements per event record, 1 .. CC_MAX_SRC_COLS (4 096) */
+    int32_t dtype;          /* CC_DT_F32, CC_DT_F64, CC_DT_U8, CC_DT_U16, CC_DT_U32 */
+    int32_t flags;          /* 0 or CC_LM_SWAPPED */
+    int32_t d;              /* selected columns, 1 .. CC_MAX_DIM */
+    const int32_t* cols;    /* d source columns in output order, each in 0 .. src_cols - 1, repeats allowed; NULL: 0 .. d - 1 */
+    const uint32_t* masks;  /* d AND masks, integer dtypes only; NULL: none */
+} cc_list_mode;
+
+/* Each entry point has the contract of its float64 sibling (arguments, errors, what happens to a group).  Refused with
+ * CC_ERR_BAD_ARG and a message that names the reason, before anything is read, launched or allocated: a null descriptor or
+ * null data, n < 0 (n == 0 where the sibling needs points: prefetch, col_minmax), d outside 1..CC_MAX_DIM, src_cols outside
+ * 1..CC_MAX_SRC_COLS, a column index outside 0 .. src_cols - 1 (d > src_cols without a column list), another dtype code,
+ * unknown flag bits, masks with a floating dtype, an extent n * src_cols * element size beyond int64.
+ * The bytes travel as whole event records, in slabs of whole 64-point tiles through the two device staging buffers of the
+ * `_f32` route (at most 32 MiB each, 16 MiB pieces in a prefetch; CHRONOCLUST_HIP_INGEST_SLAB=<events> shortens a slab).
+ * The copies are byte copies, so `data` may sit at any address: the device staging buffer starts aligned and a record is a
+ * whole multiple of its element size.  There is NO packing pass on the host, whatever src_cols / d is: a file of 60
+ * channels of which 5 are clustered moves 12 times its payload across the bus - the caller's trade (select on the host and
+ * use a `_view` or `_f32` entry point where that is the wrong one).  A channel that is not selected is never read on the
+ * device: a NaN pattern in it is no error.
+ * One kernel per slab (k_ingest_list) decodes an element - loaded as an unsigned integer of its width; with CC_LM_SWAPPED
+ * its bytes reversed; an integer ANDed with its mask, a float bit-cast; (double), exact for every type -, applies scale_ /
+ * min_ in double (two roundings), checks the stored values for NaN / Inf and writes the row-major and the dimension-major
+ * copy: what the device then holds is bit for bit what cc_points_upload holds after the same values decoded on the host.
+ * cc_points_upload_list / cc_points_prefetch_list: scale and min_ both NULL (plain) or both given (cc_points_upload_scaled).
+ * A prefetch is adopted by the cc_points_upload_list (or cc_online_list) of the same pointer, n, src_cols, dtype, flags, d,
+ * column list, masks (NULL and the defaults it stands for compare equal) and scaling; any other upload discards it.
+ * cc_col_minmax_list reduces the upload's slabs in the upload's staging buffers (the sign of a zero extremum is free, as
+ * for cc_col_minmax_view).  cc_assign_list takes the chunks cc_assign takes (cc_stats.assign_launches is the same), each
+ * through sub-slabs of at most 16 MiB of staging.
+ * cc_list_points: *out = the events taken through the `_list` entry points since cc_create (uploads, an adopted prefetch
+ * included, cc_online_list, cc_assign_list); no call clears it.  cc_f32_points and cc_view_points do not count this route;
+ * cc_stats keeps its layout. */
+int cc_points_upload_list(cc_handle* h, const cc_list_mode* lm, const double* scale, const double* min_);
+int cc_points_prefetch_list(cc_handle* h, const cc_list_mode* lm, const double* scale, const double* min_);
+int cc_col_minmax_list(cc_handle* h, const cc_list_mode* lm, double* out_min, double* out_max);
+int cc_online_list(cc_handle* h, const cc_list_mode* lm, int64_t* out_uid, int8_t* out_path);
+int cc_assign_list(cc_handle* h, const cc_list_mode* lm, int64_t* out_uid, int8_t* out_path, double* out_dist);
+int cc_list_points(cc_handle* h, int64_t* out);
 
 /* HDDStream.pcore_MC / outlier_MC (hddstream.py:56-57) in list order.
  * Any output pointer may be NULL.  cf1/cf2/cen/pref are [count, d]. */
