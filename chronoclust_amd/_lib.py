@@ -522,6 +522,23 @@ def shard_rows(n, world, rank, unit=1):
     return lo.value, hi.value
 
 
+# The takers of points by kind of source (Handle._source): (operation, kind) -> C-ABI symbol.  A described source ("view",
+# "list") has one upload that takes scale / min_ or two nulls; rows have a plain and a scaled one.
+_DESCRIBED = ("view", "list")
+_INGEST = {
+    "upload": {"f64": "cc_points_upload", "f32": "cc_points_upload_f32",
+               "view": "cc_points_upload_view", "list": "cc_points_upload_list"},
+    "upload_scaled": {"f64": "cc_points_upload_scaled", "f32": "cc_points_upload_scaled_f32",
+                      "view": "cc_points_upload_view", "list": "cc_points_upload_list"},
+    "prefetch": {"f64": "cc_points_prefetch", "f32": "cc_points_prefetch_f32",
+                 "view": "cc_points_prefetch_view", "list": "cc_points_prefetch_list"},
+    "col_minmax": {"f64": "cc_col_minmax", "f32": "cc_col_minmax_f32",
+                   "view": "cc_col_minmax_view", "list": "cc_col_minmax_list"},
+    "assign": {"f64": "cc_assign", "f32": "cc_assign_f32", "view": "cc_assign_view", "list": "cc_assign_list"},
+}
+_SCALED_REFUSAL = "points must be [n, d], scale and min_ [d]"
+
+
 class Handle(object):
     """One HDDStream state on one GPU."""
 
@@ -570,104 +587,71 @@ class Handle(object):
     def decay_downgrade(self, factor):
         self._check(self._lib.cc_decay_downgrade(self._h, float(factor)))
 
-    def points_upload(self, x):
+    def _source(self, x, refusal="points must be a 2-d array"):
+        """(kind, points, args, n, d) of what a taker of points is given: the kind of source - "list" (a ListMode), "view"
+        (an array points_view accepts), "f32" or "f64" (C-contiguous rows; everything else as a float64 copy: points_source) -,
+        the object that owns the memory, and the C arguments that describe it: (descriptor,) or (pointer, n, d)."""
         if isinstance(x, ListMode):
-            return self._upload_list(x, None, None)
+            desc = x.descriptor()
+            return ("list", x, (C.byref(desc),)) + x.shape
         x, view = points_source(x)
         if x.ndim != 2:
-            raise ValueError("points must be a 2-d array")
+            raise ValueError(refusal)
+        if view is not None:
+            return ("view", x, (C.byref(view),)) + x.shape
+        f32 = x.dtype == np.float32
+        return ("f32" if f32 else "f64", x, (_ptr(x, _fp if f32 else _dp),) + x.shape) + x.shape
+
+    def _ingest(self, op, kind, *args):
+        self._check(getattr(self._lib, _INGEST[op][kind])(self._h, *args))
+
+    def _upload(self, x, scale, min_):
+        kind, x, args, n, d = self._source(x, "points must be a 2-d array" if scale is None else _SCALED_REFUSAL)
+        op = "upload"
+        if scale is not None:
+            op, scale, min_ = "upload_scaled", _f64(scale), _f64(min_)
+            if scale.shape != (d,) or min_.shape != (d,):
+                raise ValueError(_SCALED_REFUSAL)
+        if scale is not None or kind in _DESCRIBED:  # (a descriptor's upload takes scale / min_ or two nulls)
+            args += (_ptr(scale), _ptr(min_))
         try:
-            if view is not None:
-                self._check(self._lib.cc_points_upload_view(self._h, C.byref(view), None, None))
-            elif x.dtype == np.float32:
-                self._check(self._lib.cc_points_upload_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1]))
-            else:
-                self._check(self._lib.cc_points_upload(self._h, _ptr(x), x.shape[0], x.shape[1]))
+            self._ingest(op, kind, *args)
         finally:
             self._prefetched = None  # adopted or discarded by the library: the array is no longer pinned by us
-        self._n = x.shape[0]
+        self._n = n
 
-    def _upload_list(self, lm, scale, min_):
-        """cc_points_upload_list of a ListMode, plain or scaled."""
-        desc = lm.descriptor()
-        try:
-            self._check(self._lib.cc_points_upload_list(self._h, C.byref(desc), _ptr(scale), _ptr(min_)))
-        finally:
-            self._prefetched = None
-        self._n = lm.shape[0]
-
-    def points_prefetch(self, x, scale=None, min_=None):
-        """Starts the background upload of the NEXT timepoint's points (cc_points_prefetch).  `x` must be the very
-        array (C-contiguous float64 or float32, or one points_view accepts) that is later passed to points_upload /
-        points_upload_scaled / online; the handle keeps a reference to it until then.  Contract: the array must not be
-        written to between this call and that upload - the upload is recognised by pointer, shape, layout, element type and
-        scaling, and the copy already on the device is used as it is."""
-        if isinstance(x, np.ndarray) and x.ndim == 2 and x.shape[0] == 0:
-            return
-        if isinstance(x, ListMode):
-            if x.shape[0] == 0:
-                return
-            scale = None if scale is None else _f64(scale)
-            min_ = None if min_ is None else _f64(min_)
-            self._prefetched = (x, scale, min_)
-            desc = x.descriptor()
-            self._check(self._lib.cc_points_prefetch_list(self._h, C.byref(desc), _ptr(scale), _ptr(min_)))
-            return
-        src, view = points_source(x)
-        if src is not x or x.ndim != 2:
-            raise ValueError("points_prefetch needs an [n, d] array that is taken as it lies - C-contiguous float64 or float32, "
-                             "or a layout and element type points_view accepts (it is not copied)")
-        scale = None if scale is None else _f64(scale)
-        min_ = None if min_ is None else _f64(min_)
-        self._prefetched = (x, scale, min_)  # keeps the buffers alive while the worker reads them
-        if view is not None:
-            self._check(self._lib.cc_points_prefetch_view(self._h, C.byref(view), _ptr(scale), _ptr(min_)))
-        elif x.dtype == np.float32:
-            self._check(self._lib.cc_points_prefetch_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(scale), _ptr(min_)))
-        else:
-            self._check(self._lib.cc_points_prefetch(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(scale), _ptr(min_)))
-
-    def col_minmax(self, x):
-        """Per-column (min, max) of x, NaN ignored, reduced on the device."""
-        if isinstance(x, ListMode):
-            mn = np.empty(x.shape[1], dtype=np.float64)
-            mx = np.empty(x.shape[1], dtype=np.float64)
-            desc = x.descriptor()
-            self._check(self._lib.cc_col_minmax_list(self._h, C.byref(desc), _ptr(mn), _ptr(mx)))
-            return mn, mx
-        x, view = points_source(x)
-        mn = np.empty(x.shape[1], dtype=np.float64)
-        mx = np.empty(x.shape[1], dtype=np.float64)
-        if view is not None:
-            self._check(self._lib.cc_col_minmax_view(self._h, C.byref(view), _ptr(mn), _ptr(mx)))
-        elif x.dtype == np.float32:
-            self._check(self._lib.cc_col_minmax_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(mn), _ptr(mx)))
-        else:
-            self._check(self._lib.cc_col_minmax(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(mn), _ptr(mx)))
-        return mn, mx
+    def points_upload(self, x):
+        self._upload(x, None, None)
 
     def points_upload_scaled(self, x, scale, min_):
         """points_upload of x * scale + min_ (MinMaxScaler.transform), scaled on the device."""
-        if isinstance(x, ListMode):
-            scale, min_ = _f64(scale), _f64(min_)
-            if scale.shape != (x.shape[1],) or min_.shape != (x.shape[1],):
-                raise ValueError("points must be [n, d], scale and min_ [d]")
-            return self._upload_list(x, scale, min_)
-        (x, view), scale, min_ = points_source(x), _f64(scale), _f64(min_)
-        if x.ndim != 2 or scale.shape != (x.shape[1],) or min_.shape != (x.shape[1],):
-            raise ValueError("points must be [n, d], scale and min_ [d]")
-        try:
-            if view is not None:
-                self._check(self._lib.cc_points_upload_view(self._h, C.byref(view), _ptr(scale), _ptr(min_)))
-            elif x.dtype == np.float32:
-                self._check(self._lib.cc_points_upload_scaled_f32(self._h, _ptr(x, _fp), x.shape[0], x.shape[1], _ptr(scale),
-                                                                  _ptr(min_)))
-            else:
-                self._check(self._lib.cc_points_upload_scaled(self._h, _ptr(x), x.shape[0], x.shape[1], _ptr(scale),
-                                                              _ptr(min_)))
-        finally:
-            self._prefetched = None
-        self._n = x.shape[0]
+        self._upload(x, scale, min_)
+
+    def points_prefetch(self, x, scale=None, min_=None):
+        """Starts the background upload of the NEXT timepoint's points (cc_points_prefetch).  `x` must be the very
+        array (C-contiguous float64 or float32, or one points_view accepts) or ListMode that is later passed to points_upload /
+        points_upload_scaled / online; the handle keeps a reference to it until then.  Contract: the array must not be
+        written to between this call and that upload - the upload is recognised by pointer, shape, layout, element type and
+        scaling, and the copy already on the device is used as it is."""
+        if isinstance(x, (np.ndarray, ListMode)) and x.ndim == 2 and x.shape[0] == 0:
+            return
+        refusal = ("points_prefetch needs an [n, d] array that is taken as it lies - C-contiguous float64 or float32, "
+                   "or a layout and element type points_view accepts (it is not copied)")
+        kind, src, args, n, d = self._source(x, refusal)
+        if src is not x:
+            raise ValueError(refusal)
+        scale = None if scale is None else _f64(scale)
+        min_ = None if min_ is None else _f64(min_)
+        self._prefetched = (x, scale, min_)  # keeps the buffers alive while the worker reads them
+        self._ingest("prefetch", kind, *(args + (_ptr(scale), _ptr(min_))))
+
+    def col_minmax(self, x):
+        """Per-column (min, max) of x, NaN ignored, reduced on the device."""
+        kind, x, args, n, d = self._source(x)
+        mn = np.empty(d, dtype=np.float64)
+        mx = np.empty(d, dtype=np.float64)
+        self._ingest("col_minmax", kind, *(args + (_ptr(mn), _ptr(mx))))
+        return mn, mx
 
     def points_download(self, d, scale=None, min_=None):
         """The resident points; with scale / min_, (X - min_) / scale (MinMaxScaler.inverse_transform)."""
@@ -704,24 +688,11 @@ class Handle(object):
         the table as it stands - (uid, path, dist): the creation number of the microcluster it would join (-1: it would
         create one), 0 pcore / 1 outlier / 5 outlier that the add promotes / 2 new, the projected distance to that
         microcluster (-1.0 for path 2); path and dist are None unless wanted.  Nothing of the handle changes."""
-        lm = x if isinstance(x, ListMode) else None
-        if lm is None:
-            x, view = points_source(x)
-        if x.ndim != 2:
-            raise ValueError("points must be a 2-d array")
-        n = x.shape[0]
+        kind, x, args, n, d = self._source(x)
         uid = np.empty(n, dtype=np.int64)
         path = np.empty(n, dtype=np.int8) if want_path else None
         dist = np.empty(n, dtype=np.float64) if want_dist else None
-        if lm is not None:
-            desc = lm.descriptor()
-            self._check(self._lib.cc_assign_list(self._h, C.byref(desc), _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
-        elif view is not None:
-            self._check(self._lib.cc_assign_view(self._h, C.byref(view), _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
-        elif x.dtype == np.float32:
-            self._check(self._lib.cc_assign_f32(self._h, _ptr(x, _fp), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
-        else:
-            self._check(self._lib.cc_assign(self._h, _ptr(x), n, x.shape[1], _ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist)))
+        self._ingest("assign", kind, *(args + (_ptr(uid, _i64p), _ptr(path, _i8p), _ptr(dist))))
         return uid, path, dist
 
     def count(self, kind):

@@ -2,9 +2,10 @@
 // The handle owns the HBM-resident state (microcluster table, window buffers, points, labels) and enqueues the gfx950
 // kernels of cc_online.h / cc_offline.h on its HIP streams.  No CPU fallback exists for any kernel.
 // Here: the snapshot scan's plan and dispatcher, the handle's life cycle and settings, the online and table entry points.
-// Beside it, included below: cc_handle.h (the handle, its buffers and helpers; cc_knobs.h), cc_online_run.h (one online
-// call), cc_api_points.inc, cc_api_views.inc, cc_api_list.inc, cc_api_offline.inc, cc_api_comm.inc and cc_api_assign.inc (the other
-// entry points, by concern).
+// Beside it, included below: cc_handle.h (the handle, its buffers and helpers; cc_knobs.h, cc_ingest_src.h), cc_online_run.h
+// (one online call), cc_api_points.inc, cc_api_views.inc, cc_api_list.inc, cc_api_ingest.inc (the one upload, prefetch and
+// column reduction behind those three), cc_api_offline.inc, cc_api_comm.inc and cc_api_assign.inc (the other entry points, by
+// concern).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -391,6 +392,7 @@ Rows padded_rows(cc_handle* h, hipStream_t st, Rows rows, int q, int round, int 
 #include "cc_api_points.inc"
 #include "cc_api_views.inc"
 #include "cc_api_list.inc"
+#include "cc_api_ingest.inc"
 #include "cc_api_offline.inc"
 #include "cc_api_comm.inc"
 #include "cc_api_assign.inc"

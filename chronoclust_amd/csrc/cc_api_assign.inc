@@ -3,12 +3,11 @@
 // first stream and odd ones on the second, so that a chunk's upload runs beside the previous chunk's scan.  Nothing of the
 // handle's state is written: not the table, the control block, the resident points or their labels, the window buffers, the
 // scan copies or the policy's carried state; of cc_stats only assign_points and assign_launches.  No collective is called:
-// on a handle of a group the rank's own table is read.  cc_assign_f32: the same chunks, each uploaded in single precision into
-// the set's raw buffer and taken in by k_ingest_f32 (cc_points.h) instead of the check and the transpose.
-// cc_assign_view: the same chunks again, each staged as the view lies (view_stage, cc_api_views.inc) in sub-slabs of at most
-// 16 MiB through the set's raw buffer and taken in by k_ingest.  cc_assign_list: the same chunks once more, whole event records in
-// sub-slabs of at most 16 MiB through the set's raw buffer and taken in by k_ingest_list (cc_api_list.inc).
-// (included by cc_api.hip, the one translation unit, behind cc_handle.h)
+// on a handle of a group the rank's own table is read.  float64 rows are copied, checked and transposed chunk by chunk; every
+// other source (IngestSrc: cc_assign_f32, cc_assign_view, cc_assign_list) takes the same chunks, each staged through the set's
+// raw buffer and taken in by its ingest kernel (stage_slab, ingest_launch: cc_api_ingest.inc) - float32 rows a chunk at once, a
+// view or event records in sub-slabs of at most 16 MiB.  (included by cc_api.hip, the one translation unit, behind
+// cc_api_ingest.inc)
 
 namespace {
 
@@ -32,13 +31,11 @@ int assign_segments(const cc_handle* h, int64_t chunk, int m_rows)
     return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, most), 64));
 }
 
-// vs: the points are this view (cc_assign_view; x and f32 are then unused); ls: these event records (cc_assign_list; likewise)
-int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, const ListSrc* ls, int64_t n, int d, int64_t* out_uid, int8_t* out_path,
-               double* out_dist, bool* nonfinite)
+int assign_run(cc_handle* h, const IngestSrc& src, int64_t* out_uid, int8_t* out_path, double* out_dist, bool* nonfinite)
 {
-    if (f32) h->f32_points += n;
-    if (vs) h->view_points += n;
-    if (ls) h->list_points += n;
+    const int64_t n = src.n;
+    const int d = src.d;
+    if (long long* taken = points_counter(h, src)) *taken += n;
     h->stats.assign_points = n;
     h->stats.assign_launches = 0;
     if (n == 0) return (int)CC_OK;
@@ -54,23 +51,23 @@ int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, const L
     const int S = assign_segments(h, chunk, c.m_rows);
     hipStream_t st[2] = {h->stream, h->stream2};
     const int sets = n > chunk ? 2 : 1;
-    // a view's chunk goes through the set's raw buffer in sub-slabs of at most 16 MiB of staging, whatever the view's pitch
-    const int64_t sub = vs ? std::min<int64_t>(view_slab_points(h, *vs, (size_t)16 << 20), (chunk + 63) & ~(int64_t)63)
-                      : ls ? std::min<int64_t>(list_slab_points(h, *ls, (size_t)16 << 20), (chunk + 63) & ~(int64_t)63) : 0;
+    // a staged chunk goes through the set's raw buffer: float32 rows at once, a view or event records in sub-slabs of at most
+    // 16 MiB of staging, whatever the view's pitch
+    const size_t pb = src.staged() ? src.point_bytes(false) : 0;
+    const int64_t sub = !src.staged() ? 0 : src.kind == IngestSrc::F32 ? chunk
+                      : std::min<int64_t>(slab_points(h, pb, CC_ASSIGN_STAGING), tiles_up(chunk));
     for (int q = 0; q < sets; ++q) {
         AssignBuffers::Set& b = h->asg[q];
         b.X.ensure((size_t)chunk * d); b.Xt.ensure((size_t)chunk * d);
-        if (f32) b.raw.ensure((size_t)chunk * d);
-        if (vs) b.raw.ensure(view_slab_floats(*vs, sub));
-        if (ls) b.raw.ensure(list_slab_floats(*ls, sub));
+        if (src.staged()) b.raw.ensure(slab_floats(pb, sub));
         b.uid.ensure((size_t)chunk); b.path.ensure((size_t)chunk); b.dist.ensure((size_t)chunk);
         b.part.ensure((size_t)chunk * S * 2);
         b.bad.ensure(4);
         HIPCHK(hipMemsetAsync(b.bad.p, 0, 16, st[q]));
     }
-    if (ls) {
+    if (src.kind == IngestSrc::LIST) {
         // the descriptors once, for both streams
-        list_desc_upload(h->stream, *ls, h->list_desc);
+        list_desc_upload(h->stream, src.list, h->list_desc);
         sync_stream(h, h->stream);
     }
     std::vector<char> pack;
@@ -81,25 +78,15 @@ int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, const L
         if (ci >= 2) sync_stream(h, st[q]);  // (the set's previous chunk has left its buffers)
         AssignBuffers::Set& b = h->asg[q];
         const long long tot = (long long)cn * d;
-        if (vs) {
+        if (src.staged()) {
             // (one buffer: the next sub-slab's copy follows this one's kernel in stream order)
             for (int64_t s0 = 0; s0 < cn; s0 += sub) {
                 const int64_t ns = std::min<int64_t>(sub, cn - s0);
-                view_stage(st[q], *vs, off + s0, ns, b.raw.p, pack);
-                ingest_view_launch(st[q], b.raw.p, vs->dtype, vs->cols, vs->pitch(ns), ns, s0, cn, d, (size_t)d, b.X.p, b.Xt.p,
-                                   nullptr, nullptr, b.bad.p);
+                stage_slab(st[q], src, off + s0, ns, b.raw.p, pack);
+                ingest_launch(st[q], src, b.raw.p, false, h->list_desc.p, ns, s0, cn, (size_t)d, b.X.p, b.Xt.p, nullptr, nullptr, b.bad.p);
             }
-        } else if (ls) {
-            for (int64_t s0 = 0; s0 < cn; s0 += sub) {
-                const int64_t ns = std::min<int64_t>(sub, cn - s0);
-                HIPCHK(hipMemcpyAsync(b.raw.p, ls->at(off + s0), (size_t)ns * ls->record_bytes(), hipMemcpyHostToDevice, st[q]));
-                ingest_list_launch(st[q], b.raw.p, *ls, h->list_desc.p, ns, s0, cn, (size_t)d, b.X.p, b.Xt.p, nullptr, nullptr, b.bad.p);
-            }
-        } else if (f32) {
-            HIPCHK(hipMemcpyAsync(b.raw.p, static_cast<const float*>(x) + (size_t)off * d, (size_t)tot * 4, hipMemcpyHostToDevice, st[q]));
-            ingest_launch(st[q], b.raw.p, cn, 0, cn, d, (size_t)d, b.X.p, b.Xt.p, nullptr, nullptr, b.bad.p);
         } else {
-            HIPCHK(hipMemcpyAsync(b.X.p, static_cast<const double*>(x) + (size_t)off * d, (size_t)tot * 8, hipMemcpyHostToDevice, st[q]));
+            HIPCHK(hipMemcpyAsync(b.X.p, static_cast<const double*>(src.x) + (size_t)off * d, (size_t)tot * 8, hipMemcpyHostToDevice, st[q]));
             hipLaunchKernelGGL(k_check_finite, dim3((unsigned)std::min<long long>((tot + 255) / 256, 4096)), dim3(256), 0, st[q],
                                (const double*)b.X.p, tot, b.bad.p);
             hipLaunchKernelGGL(k_transpose_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st[q], (const double*)b.X.p,
@@ -129,15 +116,16 @@ int assign_run(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, const L
     return (int)CC_OK;
 }
 
-int assign_points(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, const ListSrc* ls, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
-                  double* out_dist)
+int assign_points(cc_handle* h, const IngestSrc& src, int64_t* out_uid, int8_t* out_path, double* out_dist)
 {
-    if (!h || n < 0 || (n > 0 && (!x || !out_uid))) return CC_ERR_BAD_ARG;
+    const int64_t n = src.n;
+    const int d = src.d;
+    if (!h || n < 0 || (n > 0 && (!src.x || !out_uid))) return CC_ERR_BAD_ARG;
     if (!h->have_par) return fail(h, CC_ERR_BAD_ARG, "cc_set_params has not been called");
     if (d <= 0 || d > CC_MAX_DIM) return fail(h, CC_ERR_BAD_ARG, "d must be in 1.." + std::to_string(CC_MAX_DIM));
     if (h->hc.m_rows > 0 && d != h->d) return fail(h, CC_ERR_BAD_ARG, "dimensionality differs from the microclusters already held");
     bool nonfinite = false;
-    const int rc = guarded(h, [&]() { return assign_run(h, x, f32, vs, ls, n, d, out_uid, out_path, out_dist, &nonfinite); });
+    const int rc = guarded(h, [&]() { return assign_run(h, src, out_uid, out_path, out_dist, &nonfinite); });
     // (outside guarded: a refused query is no reason to give up the handle's group)
     if (rc == CC_OK && nonfinite) return fail(h, CC_ERR_NONFINITE, "input points contain NaN or Inf");
     return rc;
@@ -148,13 +136,13 @@ int assign_points(cc_handle* h, const void* x, bool f32, const ViewSrc* vs, cons
 extern "C" int cc_assign(cc_handle* h, const double* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
                          double* out_dist)
 {
-    return assign_points(h, x, false, nullptr, nullptr, n, d, out_uid, out_path, out_dist);
+    return assign_points(h, IngestSrc::rows(x, false, n, d), out_uid, out_path, out_dist);
 }
 
 extern "C" int cc_assign_f32(cc_handle* h, const float* x, int64_t n, int32_t d, int64_t* out_uid, int8_t* out_path,
                              double* out_dist)
 {
-    return assign_points(h, x, true, nullptr, nullptr, n, d, out_uid, out_path, out_dist);
+    return assign_points(h, IngestSrc::rows(x, true, n, d), out_uid, out_path, out_dist);
 }
 
 extern "C" int cc_assign_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path, double* out_dist)
@@ -162,7 +150,7 @@ extern "C" int cc_assign_view(cc_handle* h, const cc_points_view* view, int64_t*
     ViewSrc v;
     const int rc = view_check(h, view, false, &v);
     if (rc != CC_OK) return rc;
-    return assign_points(h, v.data, false, &v, nullptr, v.n, v.d, out_uid, out_path, out_dist);
+    return assign_points(h, IngestSrc::of(v), out_uid, out_path, out_dist);
 }
 
 extern "C" int cc_assign_list(cc_handle* h, const cc_list_mode* lm, int64_t* out_uid, int8_t* out_path, double* out_dist)
@@ -170,5 +158,5 @@ extern "C" int cc_assign_list(cc_handle* h, const cc_list_mode* lm, int64_t* out
     ListSrc v;
     const int rc = list_check(h, lm, false, &v);
     if (rc != CC_OK) return rc;
-    return assign_points(h, v.data, false, nullptr, &v, v.n, v.d, out_uid, out_path, out_dist);
+    return assign_points(h, IngestSrc::of(v), out_uid, out_path, out_dist);
 }

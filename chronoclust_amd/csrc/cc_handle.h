@@ -3,6 +3,7 @@
 // block's push / pull, and the growth of the table and the window buffers.  (included by cc_api.hip, the one translation unit)
 #pragma once
 #include "cc_knobs.h"
+#include "cc_ingest_src.h"
 
 namespace {
 
@@ -319,7 +320,7 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
     DevBuf<int8_t> lab_path;
     DevBuf<int> badflag;
     DevBuf<double> scr, scr2;  // scaler scratch
-    DevBuf<float> ingest_raw[2];  // cc_points_upload_f32: the two slabs of raw single-precision points (k_ingest_f32 reads them)
+    DevBuf<float> ingest_raw[2];  // a staged source (IngestSrc): the two slabs of device staging of an upload / a column reduction, in bytes
     long long f32_points = 0;     // cc_f32_points: points taken in single precision since cc_create
     long long view_points = 0;    // cc_view_points: points taken through the `_view` entry points since cc_create (they share ingest_raw, in bytes)
     long long list_points = 0;    // cc_list_points: events taken through the `_list` entry points since cc_create (ingest_raw again)
@@ -329,20 +330,11 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
     struct Prefetch {
         std::thread worker;
         bool active = false;            // a worker was started and has not been adopted / discarded yet
-        const void* x = nullptr;        // what it uploads: pointer, shape, scaling, element type (compared by the adopting upload)
-        long long n = 0;
-        int d = 0;
+        IngestSrc src;                  // what it uploads, and how it is read (compared by the adopting upload)
         bool scaled = false;
-        bool f32 = false;               // x is float, staged piece by piece into raw[] and taken in by k_ingest_f32
-        long long piece = 0;            // ... points per piece: whole 64-point tiles that fit a page-locked buffer
-        bool view = false;              // x is element (0, 0) of a cc_points_view of this dtype and these strides (k_ingest; pieces as for f32)
-        int dtype = 0;
-        long long rs = 0, cs = 0;
-        bool list = false;              // x is event 0 of a cc_list_mode of this dtype, these flags, src_cols and descriptors (k_ingest_list; pieces as for f32)
-        int src_cols = 0, flags = 0;
-        std::vector<cc_list_desc> ldesc;
-        DevBuf<int> desc;               // ... the descriptors on the device
-        DevBuf<float> raw[2];
+        long long piece = 0;            // a staged source: points per piece, whole 64-point tiles that fit a page-locked buffer
+        DevBuf<int> desc;               // event records: their descriptors on the device (k_ingest_list)
+        DevBuf<float> raw[2];           // a staged source: the two pieces of device staging
         std::vector<double> scale, mn;
         DevBuf<double> X, Xt, sm;       // destination buffers (swapped with the handle's on adoption), scale / min
         DevBuf<int> bad;
