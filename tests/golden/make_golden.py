@@ -24,6 +24,13 @@ Outputs
   blob_*.npz    d = 20 / 14 / 40 / 5 / 80 synthetic scenarios (inputs regenerated from
                 the seed by tests/scenarios.py) with the reference's per-point
                 labels, MC tables, clusters and result.csv text
+
+Written by scripts of their own, which reuse the Recorder of this file:
+  blob_d160.npz  make_golden_wide.py: the d = 160 blob scenario
+  surface/       make_golden_surface.py: the reference at the designed edges - the streams of test_fuzz_parity and of
+                test_sequential's k_seq_r fuzz, the decay boundary, the offline and the online phase on the small injected
+                tables of tests/table_util.py; per call the labels, paths, ids, weights and counters in full and the
+                SHA-256 of the wide float columns, many cases to a file (tests/surface_util.py reads them)
 """
 import gzip
 import hashlib

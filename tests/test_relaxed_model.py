@@ -235,15 +235,18 @@ def test_relaxed_mode_refuses_65_dimensions_on_every_rank_and_works_at_64_afterw
 
         def refuse(rank):
             h = hs[rank]
+            arrived = False
             try:
                 h.set_params(*par._replace(pi=65))
                 h.comm_set_relaxed(64)
                 h.points_upload(wide)
                 ready.wait(60)                              # (every rank is refused by its own call, not by a peer's failure)
+                arrived = True
                 h.online_run()
             except BaseException as e:  # noqa: BLE001
                 errors[rank] = e
-                ready.abort()
+                if not arrived:                             # (a rank refused after the barrier must not break it for a peer that
+                    ready.abort()                           # is still on its way out of wait(): that peer would see the abort)
 
         threads = [threading.Thread(target=refuse, args=(r,)) for r in range(world)]
         for th in threads:
