@@ -120,11 +120,54 @@ class CcListMode(C.Structure):
                 ("flags", C.c_int32), ("d", C.c_int32), ("cols", C.POINTER(C.c_int32)), ("masks", C.POINTER(C.c_uint32))]
 
 
+class CcListTransform(C.Structure):
+    """cc_list_transform: compensation and arcsinh of list-mode event records on the device."""
+    _fields_ = [("m", C.c_int32), ("reserved", C.c_int32), ("comp_cols", C.POINTER(C.c_int32)),
+                ("comp", C.POINTER(C.c_double)), ("cofactor", C.POINTER(C.c_double))]
+
+
 LM_SWAPPED = 1
 MAX_SRC_COLS = 4096
+MAX_COMP = 64
 # the element types list-mode data has, by numpy dtype in native byte order
 LIST_DTYPES = {np.dtype(t): code for t, code in (
     (np.float32, DT_F32), (np.float64, DT_F64), (np.uint8, DT_U8), (np.uint16, DT_U16), (np.uint32, DT_U32))}
+
+
+class ListTransform(object):
+    """What list-mode events take before they are clustered (cc_list_transform), applied on the device as they land:
+    comp_cols: m distinct source columns (indices into the record) and comp: [m, m], the INVERSE of their spillover matrix - a
+    selected dimension whose source column is comp_cols[i] becomes sum_j x[comp_cols[j]] * comp[j, i], summed left to right in
+    double, nothing fused; compensated columns need not be selected.  cofactor: a number for every selected dimension or one
+    per selected dimension; > 0: arcsinh(v / cofactor), 0: the value passes through.  Attached through
+    ListMode(..., transform=...).  Only the shapes are checked here; the values are the library's to refuse (ValueError)."""
+
+    def __init__(self, comp_cols=None, comp=None, cofactor=None):
+        if (comp_cols is None) != (comp is None):
+            raise ValueError("ListTransform: comp_cols and comp go together")
+        self.comp_cols = np.zeros(0, np.int32) if comp_cols is None else np.ascontiguousarray(comp_cols, dtype=np.int32)
+        m = self.m = int(self.comp_cols.size)
+        if self.comp_cols.ndim != 1:
+            raise ValueError("ListTransform: comp_cols must be a list of indices")
+        self.comp = np.zeros((0, 0)) if comp is None else np.ascontiguousarray(comp, dtype=np.float64)
+        if self.comp.shape != (m, m):
+            raise ValueError("ListTransform: comp must be [%d, %d], one row and one column per compensated column" % (m, m))
+        if cofactor is not None:
+            cofactor = np.asarray(cofactor, dtype=np.float64)
+            cofactor = cofactor if cofactor.ndim == 0 else np.ascontiguousarray(cofactor)
+            if cofactor.ndim > 1:
+                raise ValueError("ListTransform: cofactor is a number or one number per selected dimension")
+        self.cofactor = cofactor
+
+    def cofactors(self, d):
+        """The d cofactors (a number is every dimension's), or None."""
+        if self.cofactor is None:
+            return None
+        if self.cofactor.ndim == 0:
+            return np.full(d, float(self.cofactor))
+        if self.cofactor.shape != (d,):
+            raise ValueError("ListTransform: %d cofactors for %d selected dimensions" % (self.cofactor.size, d))
+        return self.cofactor
 
 
 class ListMode(object):
@@ -134,11 +177,16 @@ class ListMode(object):
     selected column; None: none).  The buffer may start at any address and is kept alive by this object; it is never copied
     or packed on the host: the `_list` entry points move whole records and the device swaps, gathers, masks and widens.
     shape == (n, d), ndim == 2; np.asarray(list_mode) is the host decode - float32 for float32 sources, else float64 -, the
-    referee of the device route and the fallback of every host-side consumer."""
+    referee of the device route and the fallback of every host-side consumer.
+    transform: a ListTransform - the records then go through the `_list_xf` entry points and are compensated and
+    arcsinh-transformed on the device.  np.asarray(list_mode) applies the transform on the host (always float64): the same
+    left-to-right sum in numpy, which IS the device's compensation bit for bit, and np.arcsinh, which agrees with the device's
+    asinh only to a few units in the last place (tests/test_fcs_transform.py keeps the measured bound), not bit for bit - so
+    what the device holds is read back from it (Handle.points_download) wherever the very values matter."""
 
     ndim = 2
 
-    def __init__(self, buffer, n, src_cols, dtype, columns=None, masks=None):
+    def __init__(self, buffer, n, src_cols, dtype, columns=None, masks=None, transform=None):
         dtype = np.dtype(dtype)
         if dtype.newbyteorder("=") not in LIST_DTYPES:
             raise ValueError("ListMode: dtype %s is none of float32, float64, uint8, uint16, uint32" % dtype)
@@ -165,6 +213,12 @@ class ListMode(object):
             if self.masks.shape != self.columns.shape:
                 raise ValueError("ListMode: one mask per selected column")
         self.shape = (n, int(self.columns.size))
+        self.transform = transform
+        self._cofactors = None
+        if transform is not None:
+            if not isinstance(transform, ListTransform):
+                raise ValueError("ListMode: transform must be a ListTransform")
+            self._cofactors = transform.cofactors(self.shape[1])
 
     def __len__(self):
         return self.n
@@ -176,13 +230,53 @@ class ListMode(object):
                           self.columns.ctypes.data_as(C.POINTER(C.c_int32)),
                           None if self.masks is None else self.masks.ctypes.data_as(C.POINTER(C.c_uint32)))
 
+    def transform_descriptor(self):
+        """The cc_list_transform of these records, or None without one (it points into this object, as descriptor())."""
+        t = self.transform
+        if t is None:
+            return None
+        return CcListTransform(t.m, 0, t.comp_cols.ctypes.data_as(C.POINTER(C.c_int32)) if t.m else None,
+                               t.comp.ctypes.data_as(C.POINTER(C.c_double)) if t.m else None,
+                               None if self._cofactors is None else self._cofactors.ctypes.data_as(C.POINTER(C.c_double)))
+
     def __array__(self, dtype=None, copy=None):
         rec = np.frombuffer(self._bytes, dtype=self.dtype, count=self.n * self.src_cols).reshape(self.n, self.src_cols)
+        native = self.dtype.newbyteorder("=")
         out = rec[:, self.columns]
         if self.masks is not None:
-            out = out.astype(self.dtype.newbyteorder("=")) & self.masks.astype(self.dtype.newbyteorder("="))
-        out = out.astype(np.float32 if self.dtype.itemsize == 4 and self.dtype.kind == "f" else np.float64)
+            out = out.astype(native) & self.masks.astype(native)
+        if self.transform is not None:
+            out = self._host_transform(rec, out.astype(np.float64))
+        else:
+            out = out.astype(np.float32 if self.dtype.itemsize == 4 and self.dtype.kind == "f" else np.float64)
         return out if dtype is None else out.astype(dtype, copy=False)
+
+    def _host_transform(self, rec, out):
+        """The transform on the host, as the device applies it: a compensated column decoded under the mask of the first
+        selected dimension that names it, the sum left to right with every product and sum rounded, then arcsinh."""
+        t = self.transform
+        native = self.dtype.newbyteorder("=")
+        cols = self.columns.tolist()
+        xs = []
+        for c in t.comp_cols.tolist():
+            x = rec[:, c].astype(native)
+            if self.masks is not None and c in cols:
+                x = x & self.masks[cols.index(c)].astype(native)
+            xs.append(x.astype(np.float64))
+        for k, c in enumerate(cols):
+            hit = np.flatnonzero(t.comp_cols == c)
+            if hit.size:
+                i = int(hit[0])
+                v = xs[0] * t.comp[0, i]
+                for j in range(1, t.m):
+                    v = v + xs[j] * t.comp[j, i]
+                out[:, k] = v
+        if self._cofactors is not None:
+            with np.errstate(all="ignore"):
+                for k, cf in enumerate(self._cofactors.tolist()):
+                    if cf > 0:
+                        out[:, k] = np.arcsinh(out[:, k] / cf)
+        return out
 
 
 class CcRelaxedStats(C.Structure):
@@ -197,6 +291,7 @@ _i32p = C.POINTER(C.c_int32)
 _i8p = C.POINTER(C.c_int8)
 _vp = C.POINTER(CcPointsView)
 _lp = C.POINTER(CcListMode)
+_xp = C.POINTER(CcListTransform)
 
 # name -> (restype, argtypes): every symbol include/chronoclust_hip.h declares
 SYMBOLS = {
@@ -236,6 +331,11 @@ SYMBOLS = {
     "cc_online_list": (C.c_int, [C.c_void_p, _lp, _i64p, _i8p]),
     "cc_assign_list": (C.c_int, [C.c_void_p, _lp, _i64p, _i8p, _dp]),
     "cc_list_points": (C.c_int, [C.c_void_p, _i64p]),
+    "cc_points_upload_list_xf": (C.c_int, [C.c_void_p, _lp, _xp, _dp, _dp]),
+    "cc_points_prefetch_list_xf": (C.c_int, [C.c_void_p, _lp, _xp, _dp, _dp]),
+    "cc_col_minmax_list_xf": (C.c_int, [C.c_void_p, _lp, _xp, _dp, _dp]),
+    "cc_online_list_xf": (C.c_int, [C.c_void_p, _lp, _xp, _i64p, _i8p]),
+    "cc_assign_list_xf": (C.c_int, [C.c_void_p, _lp, _xp, _i64p, _i8p, _dp]),
     "cc_count": (C.c_int, [C.c_void_p, C.c_int]),
     "cc_dim": (C.c_int, [C.c_void_p]),
     "cc_counters": (C.c_int, [C.c_void_p, _i64p, _i64p]),
@@ -523,18 +623,20 @@ def shard_rows(n, world, rank, unit=1):
 
 
 # The takers of points by kind of source (Handle._source): (operation, kind) -> C-ABI symbol.  A described source ("view",
-# "list") has one upload that takes scale / min_ or two nulls; rows have a plain and a scaled one.
-_DESCRIBED = ("view", "list")
+# "list", "list_xf": a ListMode with a transform) has one upload that takes scale / min_ or two nulls; rows have a plain and a
+# scaled one.
+_DESCRIBED = ("view", "list", "list_xf")
 _INGEST = {
     "upload": {"f64": "cc_points_upload", "f32": "cc_points_upload_f32",
-               "view": "cc_points_upload_view", "list": "cc_points_upload_list"},
+               "view": "cc_points_upload_view", "list": "cc_points_upload_list", "list_xf": "cc_points_upload_list_xf"},
     "upload_scaled": {"f64": "cc_points_upload_scaled", "f32": "cc_points_upload_scaled_f32",
-                      "view": "cc_points_upload_view", "list": "cc_points_upload_list"},
+                      "view": "cc_points_upload_view", "list": "cc_points_upload_list", "list_xf": "cc_points_upload_list_xf"},
     "prefetch": {"f64": "cc_points_prefetch", "f32": "cc_points_prefetch_f32",
-                 "view": "cc_points_prefetch_view", "list": "cc_points_prefetch_list"},
+                 "view": "cc_points_prefetch_view", "list": "cc_points_prefetch_list", "list_xf": "cc_points_prefetch_list_xf"},
     "col_minmax": {"f64": "cc_col_minmax", "f32": "cc_col_minmax_f32",
-                   "view": "cc_col_minmax_view", "list": "cc_col_minmax_list"},
-    "assign": {"f64": "cc_assign", "f32": "cc_assign_f32", "view": "cc_assign_view", "list": "cc_assign_list"},
+                   "view": "cc_col_minmax_view", "list": "cc_col_minmax_list", "list_xf": "cc_col_minmax_list_xf"},
+    "assign": {"f64": "cc_assign", "f32": "cc_assign_f32", "view": "cc_assign_view", "list": "cc_assign_list",
+               "list_xf": "cc_assign_list_xf"},
 }
 _SCALED_REFUSAL = "points must be [n, d], scale and min_ [d]"
 
@@ -592,7 +694,9 @@ class Handle(object):
         (an array points_view accepts), "f32" or "f64" (C-contiguous rows; everything else as a float64 copy: points_source) -,
         the object that owns the memory, and the C arguments that describe it: (descriptor,) or (pointer, n, d)."""
         if isinstance(x, ListMode):
-            desc = x.descriptor()
+            desc, xf = x.descriptor(), x.transform_descriptor()
+            if xf is not None:
+                return ("list_xf", x, (C.byref(desc), C.byref(xf))) + x.shape
             return ("list", x, (C.byref(desc),)) + x.shape
         x, view = points_source(x)
         if x.ndim != 2:

@@ -190,7 +190,9 @@ def write_datapoints_details(dataset_attributes, clusters, hddstream, raw, clust
         # the reference writes inverse_transform(transform(raw)), not raw: (X - min_) / scale_ on the device
         values = hddstream.resident_points(scaler.scale_, scaler.min_)
     elif isinstance(raw, _lib.ListMode):
-        values = hddstream.resident_points()  # (event records decoded on the device: read back, as under scaling)
+        # (event records decoded - with a `.transform` sidecar also compensated and arcsinh-transformed - on the device: read
+        # back, as under scaling; the host decode agrees with the device's asinh only to the last place or two)
+        values = hddstream.resident_points()
     else:
         values = raw
     usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)

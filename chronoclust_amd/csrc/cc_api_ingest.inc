@@ -172,8 +172,7 @@ void prefetch_worker(cc_handle::Prefetch& pf, int device, size_t xt_rows)
     const int d = s.d;
     const double* sc = pf.scaled ? pf.sm.p : nullptr;
     chk(hipMemsetAsync(pf.bad.p, 0, 16, pf.stream), "hipMemsetAsync");
-    if (s.kind == IngestSrc::LIST)
-        chk(hipMemcpyAsync(pf.desc.p, s.list.desc.data(), (size_t)d * sizeof(cc_list_desc), hipMemcpyHostToDevice, pf.stream), "hipMemcpyAsync");
+    if (s.kind == IngestSrc::LIST) chk(list_desc_copy(pf.stream, s.list, pf.desc.p), "hipMemcpyAsync");
     if (pf.scaled) {
         chk(hipMemcpyAsync(pf.sm.p, pf.scale.data(), (size_t)d * 8, hipMemcpyHostToDevice, pf.stream), "hipMemcpyAsync");
         chk(hipMemcpyAsync(pf.sm.p + d, pf.mn.data(), (size_t)d * 8, hipMemcpyHostToDevice, pf.stream), "hipMemcpyAsync");
@@ -230,7 +229,7 @@ int prefetch_source(cc_handle* h, const IngestSrc& src, const double* scale, con
         pf.pin_bytes = CC_PREFETCH_STAGING;
     }
     pf.X.ensure((size_t)n * d); pf.Xt.ensure((size_t)n * xt_dims(d)); pf.sm.ensure((size_t)2 * d); pf.bad.ensure(4);
-    if (src.kind == IngestSrc::LIST) pf.desc.ensure((size_t)2 * d);
+    if (src.kind == IngestSrc::LIST) pf.desc.ensure(src.list.desc_words());
     if (src.staged()) {
         // a piece: the whole point tiles that fit a page-locked buffer, a view's rows without their pitch
         const size_t pb = src.point_bytes(true);

@@ -1,5 +1,5 @@
 // cc_ingest_src.h — what the host knows of points that reach the device through staging: IngestSrc, one description for
-// float32 rows (`_f32`), a checked cc_points_view (`_view`) and a checked cc_list_mode (`_list`), with float64 rows - a
+// float32 rows (`_f32`), a checked cc_points_view (`_view`) and a checked cc_list_mode (`_list`, `_list_xf`), with float64 rows - a
 // whole-array copy, not staged - as its fourth kind.  The upload, the prefetch and cc_assign (cc_api_ingest.inc,
 // cc_api_assign.inc) are written once against it; cc_handle::Prefetch keeps one to tell which upload may adopt it.
 // Host data only: the staging copies and the kernel launches per kind are in cc_api_ingest.inc.
@@ -30,6 +30,15 @@ struct ListSrc {
     int64_t n = 0;
     int src_cols = 0, dtype = 0, sz = 0, flags = 0, d = 0;
     std::vector<cc_list_desc> desc;  // d of them
+    // the transform of the `_list_xf` entry points (cc_list_transform, checked), a copy: xf_f = comp[m][m], then the d
+    // cofactors where there are any; xf_i = the m compensated columns, their m masks, then per selected dimension its index
+    // into them or -1 (cc_list_xf, cc_ingest_list_xf.h).  On the device both lie behind the descriptors: xf_words() more ints.
+    bool xf = false, has_cof = false;
+    int m = 0;
+    std::vector<double> xf_f;
+    std::vector<int> xf_i;
+    size_t xf_words() const { return xf ? 2 * xf_f.size() + xf_i.size() : 0; }
+    size_t desc_words() const { return (size_t)2 * d + xf_words(); }
     bool swapped() const { return (flags & CC_LM_SWAPPED) != 0; }
     size_t record_bytes() const { return (size_t)src_cols * (size_t)sz; }
     const char* at(int64_t r) const { return data + (size_t)r * record_bytes(); }
@@ -87,7 +96,11 @@ struct IngestSrc {
         if (list.dtype != o.list.dtype || list.src_cols != o.list.src_cols || list.flags != o.list.flags) return false;
         for (int i = 0; i < d; ++i)
             if (list.desc[i].col != o.list.desc[i].col || list.desc[i].mask != o.list.desc[i].mask) return false;
-        return true;
+        // the transform by content: m, the columns, the bits of every matrix entry and cofactor
+        if (list.xf != o.list.xf || list.m != o.list.m || list.has_cof != o.list.has_cof || list.xf_i != o.list.xf_i ||
+            list.xf_f.size() != o.list.xf_f.size())
+            return false;
+        return list.xf_f.empty() || memcmp(list.xf_f.data(), o.list.xf_f.data(), list.xf_f.size() * sizeof(double)) == 0;
     }
 };
 

@@ -3,10 +3,13 @@
 read_fcs memory-maps the file, parses HEADER and TEXT and hands the DATA segment out as a `_lib.ListMode` - the bytes the
 file holds, in the file's byte order, every channel of an event interleaved - which Handle.points_upload and its kin move to
 the device as they are: the byte swap, the selection of the channels, the `$PnR` range mask and the widening happen there
-(cc_points_upload_list).  Layouts the device route does not take are decoded on the host into a float64 array."""
+(cc_points_upload_list).  Layouts the device route does not take are decoded on the host into a float64 array.
+With compensate / cofactor the file's own spillover matrix is inverted here and travels with the ListMode as a
+`_lib.ListTransform`: the compensation and arcsinh(x / cofactor) happen on the device too (cc_points_upload_list_xf);
+sidecar_transform reads the `<file>.transform` that asks for them beside a timepoint of app.run."""
 import numpy as np
 
-from ._lib import ListMode
+from ._lib import MAX_COMP, ListMode, ListTransform
 
 VERSIONS = (b"FCS2.0", b"FCS3.0", b"FCS3.1")
 
@@ -136,7 +139,96 @@ def _host_decode(raw, tot, par, datatype, widths, order, masks):
     return out
 
 
-def read_fcs(path, columns=None):
+SPILLOVER_KEYWORDS = ("$SPILLOVER", "$SPILL", "SPILL")
+
+
+def parse_spillover(text, names):
+    """(keyword, channel indices, spillover matrix [n, n]) of the file's own spillover keyword - $SPILLOVER, else $SPILL, else
+    SPILL: `n,name_1..name_n,` and n * n values, row-major; the names matched against `names` (the $PnN).  ValueError naming
+    the keyword where it is absent, malformed or names an unknown channel."""
+    key = next((k for k in SPILLOVER_KEYWORDS if k in text), None)
+    if key is None:
+        raise ValueError("FCS TEXT: compensation asked for, but none of %s is present" % ", ".join(SPILLOVER_KEYWORDS))
+    fields = [f.strip() for f in text[key].split(",")]
+    try:
+        n = int(fields[0])
+    except ValueError:
+        raise ValueError("FCS TEXT: %s does not begin with a channel count (%r)" % (key, fields[0])) from None
+    if n < 1:
+        raise ValueError("FCS TEXT: %s names %d channels" % (key, n))
+    if n > MAX_COMP:
+        raise ValueError("FCS TEXT: %s names %d channels, at most %d are taken" % (key, n, MAX_COMP))
+    if len(fields) != 1 + n + n * n:
+        raise ValueError("FCS TEXT: %s holds %d fields, %d channels need %d" % (key, len(fields), n, 1 + n + n * n))
+    idx = []
+    for name in fields[1:1 + n]:
+        if name not in names:
+            raise ValueError("FCS TEXT: %s names channel %r, which is no $PnN (channels: %s)" % (key, name, ", ".join(names)))
+        idx.append(names.index(name))
+    if len(set(idx)) != n:
+        raise ValueError("FCS TEXT: %s names a channel twice" % key)
+    try:
+        values = [float(v) for v in fields[1 + n:]]
+    except ValueError:
+        raise ValueError("FCS TEXT: %s holds a value that is no number" % key) from None
+    spill = np.array(values, np.float64).reshape(n, n)
+    if not np.isfinite(spill).all():
+        raise ValueError("FCS TEXT: %s holds a value that is not finite" % key)
+    return key, idx, spill
+
+
+def _compensation(text, names):
+    """(channel indices, inverse spillover matrix) for read_fcs(compensate=True)."""
+    key, idx, spill = parse_spillover(text, names)
+    try:
+        inv = np.linalg.inv(spill)
+    except np.linalg.LinAlgError:
+        raise ValueError("FCS TEXT: the matrix of %s is singular" % key) from None
+    if not np.isfinite(inv).all():
+        raise ValueError("FCS TEXT: the matrix of %s is singular" % key)
+    return idx, np.ascontiguousarray(inv)
+
+
+def _cofactors(cofactor, picked):
+    """One cofactor per selected channel: a number for all, or a dict from channel name to number (unnamed channels: 0)."""
+    if cofactor is None:
+        return None
+    if isinstance(cofactor, dict):
+        unknown = [k for k in cofactor if k not in picked]
+        if unknown:
+            raise ValueError("FCS: cofactor names %r, which is no selected channel (selected: %s)" % (unknown[0], ", ".join(picked)))
+        out = np.array([float(cofactor.get(name, 0.0)) for name in picked], np.float64)
+    else:
+        out = np.full(len(picked), float(cofactor), np.float64)
+    if not np.isfinite(out).all() or (out < 0).any():
+        raise ValueError("FCS: a cofactor is negative or not finite")
+    return out
+
+
+def _refuse_amplified(text, channels, names):
+    """With a transform asked for, $PnE other than 0,0 and $PnG other than 1 stay unapplied - but no longer silently."""
+    for c in channels:
+        e = text.get("$P%dE" % (c + 1))
+        if e is not None:
+            try:
+                flat = [float(v) for v in e.split(",")] == [0.0, 0.0]
+            except ValueError:
+                flat = False
+            if not flat:
+                raise ValueError("FCS TEXT: $P%dE is %s (channel %s): logarithmic amplification is not applied, so the channel "
+                                 "takes no compensation or cofactor" % (c + 1, e.strip(), names[c]))
+        g = text.get("$P%dG" % (c + 1))
+        if g is not None:
+            try:
+                unit = float(g) == 1.0
+            except ValueError:
+                unit = False
+            if not unit:
+                raise ValueError("FCS TEXT: $P%dG is %s (channel %s): linear gain is not applied, so the channel takes no "
+                                 "compensation or cofactor" % (c + 1, g.strip(), names[c]))
+
+
+def read_fcs(path, columns=None, compensate=False, cofactor=None):
     """(points, names, text) of a list-mode FCS file.
 
     points: the DATA segment as a `_lib.ListMode` over the memory-mapped file - nothing is decoded or copied on the host -
@@ -149,6 +241,15 @@ def read_fcs(path, columns=None):
     names: the $PnN of the channels taken.  text: the TEXT segment's keywords (upper-cased) and values.
     The values are the channel values AS STORED: the amplification keywords $PnE (logarithmic decades) and $PnG (linear gain)
     are NOT applied.
+    compensate: the file's own spillover matrix ($SPILLOVER, else $SPILL, else SPILL: `n,name_1..name_n,` and n * n values,
+    row-major, the names matched against $PnN) is inverted (numpy.linalg.inv) and the channels it names are compensated -
+    whether they are selected or not, every one of them is read.  cofactor: a number for every selected channel or a dict
+    from channel name ($PnN of a selected channel) to number, unnamed channels 0 - arcsinh(value / cofactor) where it is
+    positive, the value as it is where it is 0 (5 for mass cytometry, about 150 for flow).  With either, `points` is a
+    ListMode with that transform (`_lib.ListTransform`: applied on the device as the events land), or, for a layout that
+    takes the host route, the float64 array with the transform applied on the host; a selected or compensated channel whose
+    $PnE is not 0,0 or whose $PnG is present and not 1 is a ValueError naming it, and so is a spillover keyword that is
+    absent, malformed, names an unknown channel or holds a singular matrix.  Without either nothing changes.
     ValueError naming the keyword for: $DATATYPE A, a $MODE other than L, a DATA segment shorter than $TOT * $PAR elements,
     channel widths that are no whole bytes, a malformed HEADER or TEXT."""
     mm = np.memmap(path, dtype=np.uint8, mode="c")  # (copy-on-write: the pages are the file's until somebody writes, nobody does)
@@ -199,6 +300,12 @@ def read_fcs(path, columns=None):
     sel = _select(columns, names, stains)
     picked = [names[c] for c in sel]
     raw = mm[data_lo:data_lo + tot * event_bytes]
+    transform = comp_idx = None
+    if compensate or cofactor is not None:
+        comp_idx, inv = _compensation(text, names) if compensate else ([], None)
+        cof = _cofactors(cofactor, picked)
+        _refuse_amplified(text, list(dict.fromkeys(sel + comp_idx)), names)
+        transform = ListTransform(comp_cols=comp_idx if compensate else None, comp=inv, cofactor=cof)
     ascending, descending = order == sorted(order), order == sorted(order, reverse=True)
     uniform = len(set(widths)) == 1 and widths[0] in ((32,) if datatype == "F" else (64,) if datatype == "D" else (8, 16, 32))
     if uniform and (ascending or descending):
@@ -209,10 +316,18 @@ def read_fcs(path, columns=None):
             got = [range_mask(_int(text, "$P%dR" % (c + 1)), widths[0]) for c in sel]
             if any(m is not None for m in got):
                 masks = [0xFFFFFFFF if m is None else m for m in got]
-        return ListMode(raw, tot, par, dtype, columns=sel, masks=masks), picked, text
+            # (a compensated channel that is not selected is read without a mask on the device: where its range asks for
+            # one, the file takes the host route below)
+            if any(c not in sel and range_mask(_int(text, "$P%dR" % (c + 1)), widths[0]) is not None for c in comp_idx or ()):
+                uniform = False
+    if uniform and (ascending or descending):
+        return ListMode(raw, tot, par, dtype, columns=sel, masks=masks, transform=transform), picked, text
     # the layouts of old, on the host
     masks = [range_mask(_int(text, "$P%dR" % (c + 1)), widths[c]) if datatype == "I" else None for c in range(par)]
     out = _host_decode(raw, tot, par, datatype, widths, order, masks)
+    if transform is not None:
+        # the host transform of ListMode, over the decoded channels: a native float64 record of every channel
+        return np.asarray(ListMode(np.ascontiguousarray(out), tot, par, np.float64, columns=sel, transform=transform)), picked, text
     return np.ascontiguousarray(out[:, sel]), picked, text
 
 
@@ -224,3 +339,27 @@ def sidecar_columns(path):
         return None
     with open(names_file) as f:
         return [line.strip() for line in f if line.strip()]
+
+
+def sidecar_transform(path):
+    """The transform in `<file>.transform`, as keyword arguments of read_fcs, or None without that file.  The file is JSON:
+    {"compensate": bool, "cofactor": number | {channel name: number}}, either key optional."""
+    import json
+    import os
+    name = str(path) + ".transform"
+    if not os.path.exists(name):
+        return None
+    with open(name) as f:
+        try:
+            spec = json.load(f)
+        except ValueError as e:
+            raise ValueError("%s: not JSON (%s)" % (name, e)) from None
+    if not isinstance(spec, dict) or set(spec) - {"compensate", "cofactor"}:
+        raise ValueError('%s: expected {"compensate": bool, "cofactor": number or {name: number}}' % name)
+    compensate, cofactor = spec.get("compensate", False), spec.get("cofactor")
+    if not isinstance(compensate, bool):
+        raise ValueError("%s: compensate must be true or false" % name)
+    numbers = list(cofactor.values()) if isinstance(cofactor, dict) else [] if cofactor is None else [cofactor]
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in numbers):
+        raise ValueError("%s: cofactor must be a number or an object of channel name: number" % name)
+    return dict(compensate=compensate, cofactor=cofactor)

@@ -17,10 +17,12 @@ def read_timepoint(filename):
     single precision at the source; the device widens them), anything else becomes float64.  `.fcs` files (fcs.read_fcs) come
     back as a `_lib.ListMode` over the memory-mapped DATA segment - the device decodes it - or, for the layouts that route
     does not take, as a float64 array decoded on the host; `<file>.columns` (one name per line, matched against $PnN, then
-    $PnS) selects and orders the channels, without it all channels are taken in file order."""
+    $PnS) selects and orders the channels, without it all channels are taken in file order; `<file>.transform` (JSON:
+    {"compensate": bool, "cofactor": number | {name: number}}, fcs.sidecar_transform) asks for the file's own spillover
+    compensation and arcsinh(x / cofactor), applied on the device as the events land (read_fcs)."""
     if str(filename).lower().endswith(".fcs"):
-        from ..fcs import read_fcs, sidecar_columns
-        return read_fcs(filename, columns=sidecar_columns(filename))[0]
+        from ..fcs import read_fcs, sidecar_columns, sidecar_transform
+        return read_fcs(filename, columns=sidecar_columns(filename), **(sidecar_transform(filename) or {}))[0]
     if str(filename).endswith(".npy"):
         X = np.load(filename)
         return np.ascontiguousarray(X, dtype=np.float32 if X.dtype == np.float32 else np.float64)

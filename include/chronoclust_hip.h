@@ -16,7 +16,9 @@
  *    the `_view` entry points: a cc_points_view - rows or columns, nine element
  *    types -, widened on the device; the `_list` entry points: a cc_list_mode -
  *    list-mode event records as an FCS file holds them, either byte order, a
- *    list of channels -, decoded on the device);
+ *    list of channels -, decoded on the device; the `_list_xf` entry points: the
+ *    same with a cc_list_transform - spillover compensation and
+ *    asinh(x / cofactor) -, applied on the device as the events are decoded);
  *  - one handle = one HDDStream state on one GPU; a handle is not thread-safe;
  *  - all floating-point work is IEEE double, no FMA contraction, sums over
  *    dimensions strictly left to right, so results are bit-identical to the
@@ -335,6 +337,46 @@ int cc_col_minmax_list(cc_handle* h, const cc_list_mode* lm, double* out_min, do
 int cc_online_list(cc_handle* h, const cc_list_mode* lm, int64_t* out_uid, int8_t* out_path);
 int cc_assign_list(cc_handle* h, const cc_list_mode* lm, int64_t* out_uid, int8_t* out_path, double* out_dist);
 int cc_list_points(cc_handle* h, int64_t* out);
+
+/* List-mode event records, compensated and arcsinh-transformed on the device: what a cytometry file takes before it is
+ * clustered, done where the events land.  For one event let x[s] be the decoded stored value of source column s (the decoding
+ * of the `_list` entry points: swap, AND mask, bit-cast or widening; exact in double).
+ *   compensation  m distinct source columns comp_cols[0 .. m - 1] and comp[m][m], row-major: the INVERSE of the spillover
+ *                 matrix (the caller inverts).  A selected dimension whose source column is comp_cols[i] holds
+ *                 v = ((x[comp_cols[0]] * comp[0][i]) + x[comp_cols[1]] * comp[1][i]) + ...  in ascending j, every product
+ *                 and every sum rounded to double, nothing fused, the accumulator starting as the first product; any other
+ *                 selected dimension holds v = x.  Compensated columns need not be selected, but they are read: a NaN in
+ *                 one reaches the selected values and the upload is refused with CC_ERR_NONFINITE.  An integer compensated
+ *                 column is decoded under the mask of the first selected dimension that names it; one that no selected
+ *                 dimension names, under none.  m = 0: no compensation.
+ *   cofactor      d entries, one per selected dimension, or NULL for none.  cofactor[c] > 0: v = asinh(v / cofactor[c]) - one
+ *                 double division, the device maths library's asinh (its measured distance from the
+ *                 correctly rounded value); cofactor[c] == 0: the value passes through untouched.
+ * scale / min_, the finiteness flag, the magnitude maximum and both resident copies follow as for the `_list` entry points;
+ * the two copies hold the same doubles (each value is computed once).  cc_col_minmax_list_xf reduces the transformed,
+ * unscaled values - the very doubles the plain upload holds.
+ * Each entry point is its `_list` sibling with a transform; xf == NULL (or m == 0 and cofactor == NULL) IS the sibling.  Refused
+ * with CC_ERR_BAD_ARG and a message that names the reason, before anything is read or launched, beside the sibling's refusals:
+ * m outside 0 .. CC_MAX_COMP, comp_cols or comp NULL with m > 0, a comp_cols entry outside 0 .. src_cols - 1 or one that
+ * repeats, a matrix entry that is not finite, a cofactor that is negative or not finite, reserved != 0.
+ * A prefetch is adopted only by the upload with the same transform: m, the columns, and the bits of every matrix entry and
+ * cofactor.  cc_list_points counts these events too; a group of ranks behaves as with the `_list` siblings. */
+#define CC_MAX_COMP 64
+typedef struct cc_list_transform {
+    int32_t m;                 /* compensated source columns, 0 .. CC_MAX_COMP; 0: no compensation */
+    int32_t reserved;          /* 0 */
+    const int32_t* comp_cols;  /* m distinct source columns, each in 0 .. src_cols - 1 */
+    const double* comp;        /* [m][m] row-major: the inverse of the spillover matrix */
+    const double* cofactor;    /* d entries (> 0: asinh(v / cofactor), 0: pass through), or NULL for none */
+} cc_list_transform;
+int cc_points_upload_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const double* scale,
+                             const double* min_);
+int cc_points_prefetch_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const double* scale,
+                               const double* min_);
+int cc_col_minmax_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, double* out_min, double* out_max);
+int cc_online_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, int64_t* out_uid, int8_t* out_path);
+int cc_assign_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, int64_t* out_uid, int8_t* out_path,
+                      double* out_dist);
 
 /* HDDStream.pcore_MC / outlier_MC (hddstream.py:56-57) in list order.
  * Any output pointer may be NULL.  cf1/cf2/cen/pref are [count, d]. */
