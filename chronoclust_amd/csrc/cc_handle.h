@@ -500,7 +500,10 @@ void ensure_table(cc_handle* h, size_t rows)
     if (rows > max_rows)
         throw CapacityErr{"a table of " + std::to_string(rows) + " rows of " + std::to_string(h->d) + " dimensions: more than " +
                           std::to_string(max_rows) + " rows (" + std::to_string(CC_MAX_TABLE_ELEMS) + " elements) at this width"};
-    size_t want = std::min(max_rows, std::max<size_t>(rows, std::max<size_t>(1024, h->tab.cap * 2)));
+    // (a table of another width is a new table - set_dim admits the change only while no row is held -: sized by what is asked
+    // for.  Twice the capacity of the old width, per change of width, took a handle that met a dozen widths out of memory.)
+    const size_t doubled = h->tab.d == h->d ? h->tab.cap * 2 : 0;
+    size_t want = std::min(max_rows, std::max<size_t>(rows, std::max<size_t>(1024, doubled)));
     TableStore nt;
     nt.alloc(want, h->d);
     const size_t m = (size_t)h->hc.m_rows;
@@ -529,6 +532,8 @@ int set_dim(cc_handle* h, int d)
     return CC_OK;
 }
 
+// (Known limitation: sized by the largest window times the largest width the handle has seen, also for the 64 points the wide
+// path asks for - DESIGN.md section 3.)
 void ensure_window_buffers(cc_handle* h, int win, int seg)
 {
     if (win <= h->win_alloc && seg <= h->seg_alloc && h->d <= h->d_alloc) return;
