@@ -126,6 +126,11 @@ class CcListTransform(C.Structure):
                 ("comp", C.POINTER(C.c_double)), ("cofactor", C.POINTER(C.c_double))]
 
 
+class CcListLogicle(C.Structure):
+    """cc_list_logicle: the logicle scale of list-mode event records on the device, one row T, W, M, A per selected dimension."""
+    _fields_ = [("d", C.c_int32), ("reserved", C.c_int32), ("twma", C.POINTER(C.c_double))]
+
+
 LM_SWAPPED = 1
 MAX_SRC_COLS = 4096
 MAX_COMP = 64
@@ -139,10 +144,14 @@ class ListTransform(object):
     comp_cols: m distinct source columns (indices into the record) and comp: [m, m], the INVERSE of their spillover matrix - a
     selected dimension whose source column is comp_cols[i] becomes sum_j x[comp_cols[j]] * comp[j, i], summed left to right in
     double, nothing fused; compensated columns need not be selected.  cofactor: a number for every selected dimension or one
-    per selected dimension; > 0: arcsinh(v / cofactor), 0: the value passes through.  Attached through
-    ListMode(..., transform=...).  Only the shapes are checked here; the values are the library's to refuse (ValueError)."""
+    per selected dimension; > 0: arcsinh(v / cofactor), 0: the value passes through.  logicle: one (T, W, M, A) for every
+    selected dimension, or a [d, 4] array whose rows with T == 0 leave their dimension off the scale - the logicle (biexponential)
+    display scale of Moore and Parks 2012 on the unit scale (T maps to 1, 0 to x1 = (A + W) / (M + A)), after the compensation,
+    in the place of a cofactor: a dimension takes one or the other (ListMode refuses one that carries both).  Attached through
+    ListMode(..., transform=...).  Only the shapes are checked here and the values are the library's to refuse (ValueError) -
+    but for the logicle rows, which the library checks at once (logicle_coefficients: no GPU needed)."""
 
-    def __init__(self, comp_cols=None, comp=None, cofactor=None):
+    def __init__(self, comp_cols=None, comp=None, cofactor=None, logicle=None):
         if (comp_cols is None) != (comp is None):
             raise ValueError("ListTransform: comp_cols and comp go together")
         self.comp_cols = np.zeros(0, np.int32) if comp_cols is None else np.ascontiguousarray(comp_cols, dtype=np.int32)
@@ -158,6 +167,23 @@ class ListTransform(object):
             if cofactor.ndim > 1:
                 raise ValueError("ListTransform: cofactor is a number or one number per selected dimension")
         self.cofactor = cofactor
+        if logicle is not None:
+            logicle = np.ascontiguousarray(logicle, dtype=np.float64)
+            if logicle.shape != (4,) and (logicle.ndim != 2 or logicle.shape[1] != 4):
+                raise ValueError("ListTransform: logicle is one (T, W, M, A) or a [d, 4] array of them")
+            for row in logicle.reshape(-1, 4):
+                logicle_coefficients(row)  # (the library's own refusals, before any handle exists: ValueError)
+        self.logicle = logicle
+
+    def logicles(self, d):
+        """The d rows T, W, M, A ([d, 4]; one row given is every dimension's), or None."""
+        if self.logicle is None:
+            return None
+        if self.logicle.ndim == 1:
+            return np.ascontiguousarray(np.tile(self.logicle, (d, 1)))
+        if self.logicle.shape != (d, 4):
+            raise ValueError("ListTransform: %d logicle rows for %d selected dimensions" % (self.logicle.shape[0], d))
+        return self.logicle
 
     def cofactors(self, d):
         """The d cofactors (a number is every dimension's), or None."""
@@ -182,7 +208,11 @@ class ListMode(object):
     arcsinh-transformed on the device.  np.asarray(list_mode) applies the transform on the host (always float64): the same
     left-to-right sum in numpy, which IS the device's compensation bit for bit, and np.arcsinh, which agrees with the device's
     asinh only to a few units in the last place (tests/test_fcs_transform.py keeps the measured bound), not bit for bit - so
-    what the device holds is read back from it (Handle.points_download) wherever the very values matter."""
+    what the device holds is read back from it (Handle.points_download) wherever the very values matter.
+    With a logicle row that is on (T > 0) the records go through the `_list_xl` entry points and the scale is solved on the
+    device; np.asarray(list_mode) solves it in numpy from the library's own coefficients (logicle_coefficients), the same
+    iteration with numpy's expm1 and log: device and host each lie within a few units of np.spacing(max(|y|, 0.5)) of the true
+    root and agree to the sum of their bounds, not bit for bit."""
 
     ndim = 2
 
@@ -214,11 +244,18 @@ class ListMode(object):
                 raise ValueError("ListMode: one mask per selected column")
         self.shape = (n, int(self.columns.size))
         self.transform = transform
-        self._cofactors = None
+        self._cofactors = self._logicle = None
         if transform is not None:
             if not isinstance(transform, ListTransform):
                 raise ValueError("ListMode: transform must be a ListTransform")
             self._cofactors = transform.cofactors(self.shape[1])
+            self._logicle = transform.logicles(self.shape[1])
+            if self._logicle is not None and not (self._logicle[:, 0] != 0).any():
+                self._logicle = None  # (every row off: the `_list_xf` sibling)
+            if self._logicle is not None and self._cofactors is not None:
+                both = np.flatnonzero((self._logicle[:, 0] != 0) & (self._cofactors > 0))
+                if both.size:
+                    raise ValueError("ListMode: dimension %d has a cofactor and a logicle scale" % both[0])
 
     def __len__(self):
         return self.n
@@ -238,6 +275,12 @@ class ListMode(object):
         return CcListTransform(t.m, 0, t.comp_cols.ctypes.data_as(C.POINTER(C.c_int32)) if t.m else None,
                                t.comp.ctypes.data_as(C.POINTER(C.c_double)) if t.m else None,
                                None if self._cofactors is None else self._cofactors.ctypes.data_as(C.POINTER(C.c_double)))
+
+    def logicle_descriptor(self):
+        """The cc_list_logicle of these records, or None where no row is on (it points into this object, as descriptor())."""
+        if self._logicle is None:
+            return None
+        return CcListLogicle(self.shape[1], 0, self._logicle.ctypes.data_as(C.POINTER(C.c_double)))
 
     def __array__(self, dtype=None, copy=None):
         rec = np.frombuffer(self._bytes, dtype=self.dtype, count=self.n * self.src_cols).reshape(self.n, self.src_cols)
@@ -276,7 +319,63 @@ class ListMode(object):
                 for k, cf in enumerate(self._cofactors.tolist()):
                     if cf > 0:
                         out[:, k] = np.arcsinh(out[:, k] / cf)
+        if self._logicle is not None:
+            for k, row in enumerate(self._logicle):
+                if row[0] != 0:
+                    out[:, k] = logicle_host(out[:, k], row)
         return out
+
+
+LOGICLE_STEPS = 4  # (CC_LOGICLE_STEPS of csrc/cc_ingest_list_xf.h)
+
+
+def logicle_coefficients(twma):
+    """cc_logicle_coefficients: (x1, b, d, pa, pc) of one logicle scale (T, W, M, A) as the kernels receive them, derived by the
+    library (no GPU needed); all zeros for T == 0.  ValueError for parameters outside the contract: T >= 0, M > 0, 0 <= W,
+    2 W <= M, -W <= A <= M - 2 W, all finite."""
+    twma = np.ascontiguousarray(twma, dtype=np.float64)
+    if twma.shape != (4,):
+        raise ValueError("logicle_coefficients: one (T, W, M, A)")
+    out = np.zeros(8)
+    rc = load().cc_logicle_coefficients(twma.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != 0:
+        raise ValueError("logicle (T, W, M, A) = %r is outside T >= 0, M > 0, 0 <= W, 2 W <= M, -W <= A <= M - 2 W, all finite"
+                         % (tuple(twma.tolist()),))
+    return tuple(out[:5].tolist())
+
+
+def logicle_host(v, twma):
+    """logicle(v) of a float64 array on the host, vectorised: cc_logicle_value of csrc/cc_ingest_list_xf.h restated in numpy -
+    the same start, the same LOGICLE_STEPS Halley steps in the expm1 form, the same operations in the same order - from the
+    library's own coefficients, in pieces of 64 Ki values so that the temporaries stay in cache.  A NaN or Inf gives a
+    non-finite result."""
+    x1, b, d, pa, pc = logicle_coefficients(twma)
+    v = np.asarray(v, dtype=np.float64)
+    flat = np.ascontiguousarray(v).reshape(-1)
+    out = np.empty_like(flat)
+    kc = pc / pa
+    kd = kc * d
+    with np.errstate(all="ignore"):
+        for at in range(0, flat.size, 1 << 16):
+            w = flat[at:at + (1 << 16)]
+            y = np.abs(w)
+            r = y / pa
+            u = np.minimum(r / (b + kd), np.log(r + 1.0) / b)
+            for _ in range(LOGICLE_STEPS):
+                e1 = np.expm1(b * u)
+                e2 = np.expm1(-(d * u))
+                f = (e1 - kc * e2) - r
+                p1 = b * (e1 + 1.0)
+                p2 = kd * (e2 + 1.0)
+                f1 = p1 + p2
+                f2 = b * p1 - d * p2
+                q = f / f1
+                u = u - q / (1.0 - 0.5 * (q * (f2 / f1)))
+            far = ~(r <= 2.0 ** 900)
+            if far.any():
+                u[far] = (np.log(y[far]) - np.log(pa)) / b
+            out[at:at + (1 << 16)] = np.where(w < 0.0, x1 - u, x1 + u)
+    return out.reshape(v.shape)
 
 
 class CcRelaxedStats(C.Structure):
@@ -292,6 +391,7 @@ _i8p = C.POINTER(C.c_int8)
 _vp = C.POINTER(CcPointsView)
 _lp = C.POINTER(CcListMode)
 _xp = C.POINTER(CcListTransform)
+_gp = C.POINTER(CcListLogicle)
 
 # name -> (restype, argtypes): every symbol include/chronoclust_hip.h declares
 SYMBOLS = {
@@ -336,6 +436,12 @@ SYMBOLS = {
     "cc_col_minmax_list_xf": (C.c_int, [C.c_void_p, _lp, _xp, _dp, _dp]),
     "cc_online_list_xf": (C.c_int, [C.c_void_p, _lp, _xp, _i64p, _i8p]),
     "cc_assign_list_xf": (C.c_int, [C.c_void_p, _lp, _xp, _i64p, _i8p, _dp]),
+    "cc_points_upload_list_xl": (C.c_int, [C.c_void_p, _lp, _xp, _gp, _dp, _dp]),
+    "cc_points_prefetch_list_xl": (C.c_int, [C.c_void_p, _lp, _xp, _gp, _dp, _dp]),
+    "cc_col_minmax_list_xl": (C.c_int, [C.c_void_p, _lp, _xp, _gp, _dp, _dp]),
+    "cc_online_list_xl": (C.c_int, [C.c_void_p, _lp, _xp, _gp, _i64p, _i8p]),
+    "cc_assign_list_xl": (C.c_int, [C.c_void_p, _lp, _xp, _gp, _i64p, _i8p, _dp]),
+    "cc_logicle_coefficients": (C.c_int, [_dp, _dp]),
     "cc_count": (C.c_int, [C.c_void_p, C.c_int]),
     "cc_dim": (C.c_int, [C.c_void_p]),
     "cc_counters": (C.c_int, [C.c_void_p, _i64p, _i64p]),
@@ -623,20 +729,24 @@ def shard_rows(n, world, rank, unit=1):
 
 
 # The takers of points by kind of source (Handle._source): (operation, kind) -> C-ABI symbol.  A described source ("view",
-# "list", "list_xf": a ListMode with a transform) has one upload that takes scale / min_ or two nulls; rows have a plain and a
-# scaled one.
-_DESCRIBED = ("view", "list", "list_xf")
+# "list", "list_xf": a ListMode with a transform, "list_xl": one whose transform has a logicle row that is on) has one upload that
+# takes scale / min_ or two nulls; rows have a plain and a scaled one.
+_DESCRIBED = ("view", "list", "list_xf", "list_xl")
 _INGEST = {
     "upload": {"f64": "cc_points_upload", "f32": "cc_points_upload_f32",
-               "view": "cc_points_upload_view", "list": "cc_points_upload_list", "list_xf": "cc_points_upload_list_xf"},
+               "view": "cc_points_upload_view", "list": "cc_points_upload_list", "list_xf": "cc_points_upload_list_xf",
+               "list_xl": "cc_points_upload_list_xl"},
     "upload_scaled": {"f64": "cc_points_upload_scaled", "f32": "cc_points_upload_scaled_f32",
-                      "view": "cc_points_upload_view", "list": "cc_points_upload_list", "list_xf": "cc_points_upload_list_xf"},
+                      "view": "cc_points_upload_view", "list": "cc_points_upload_list", "list_xf": "cc_points_upload_list_xf",
+                      "list_xl": "cc_points_upload_list_xl"},
     "prefetch": {"f64": "cc_points_prefetch", "f32": "cc_points_prefetch_f32",
-                 "view": "cc_points_prefetch_view", "list": "cc_points_prefetch_list", "list_xf": "cc_points_prefetch_list_xf"},
+                 "view": "cc_points_prefetch_view", "list": "cc_points_prefetch_list", "list_xf": "cc_points_prefetch_list_xf",
+                 "list_xl": "cc_points_prefetch_list_xl"},
     "col_minmax": {"f64": "cc_col_minmax", "f32": "cc_col_minmax_f32",
-                   "view": "cc_col_minmax_view", "list": "cc_col_minmax_list", "list_xf": "cc_col_minmax_list_xf"},
+                   "view": "cc_col_minmax_view", "list": "cc_col_minmax_list", "list_xf": "cc_col_minmax_list_xf",
+                   "list_xl": "cc_col_minmax_list_xl"},
     "assign": {"f64": "cc_assign", "f32": "cc_assign_f32", "view": "cc_assign_view", "list": "cc_assign_list",
-               "list_xf": "cc_assign_list_xf"},
+               "list_xf": "cc_assign_list_xf", "list_xl": "cc_assign_list_xl"},
 }
 _SCALED_REFUSAL = "points must be [n, d], scale and min_ [d]"
 
@@ -690,11 +800,14 @@ class Handle(object):
         self._check(self._lib.cc_decay_downgrade(self._h, float(factor)))
 
     def _source(self, x, refusal="points must be a 2-d array"):
-        """(kind, points, args, n, d) of what a taker of points is given: the kind of source - "list" (a ListMode), "view"
+        """(kind, points, args, n, d) of what a taker of points is given: the kind of source - "list" (a ListMode; "list_xf"
+        with a transform, "list_xl" with a logicle row that is on), "view"
         (an array points_view accepts), "f32" or "f64" (C-contiguous rows; everything else as a float64 copy: points_source) -,
         the object that owns the memory, and the C arguments that describe it: (descriptor,) or (pointer, n, d)."""
         if isinstance(x, ListMode):
-            desc, xf = x.descriptor(), x.transform_descriptor()
+            desc, xf, lg = x.descriptor(), x.transform_descriptor(), x.logicle_descriptor()
+            if lg is not None:
+                return ("list_xl", x, (C.byref(desc), C.byref(xf), C.byref(lg))) + x.shape
             if xf is not None:
                 return ("list_xf", x, (C.byref(desc), C.byref(xf))) + x.shape
             return ("list", x, (C.byref(desc),)) + x.shape

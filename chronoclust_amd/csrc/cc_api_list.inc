@@ -1,10 +1,12 @@
-// cc_api_list.inc — the `_list` and `_list_xf` entry points: list-mode event records (cc_list_mode: the DATA segment of an FCS file) to the
+// cc_api_list.inc — the `_list`, `_list_xf` and `_list_xl` entry points: list-mode event records (cc_list_mode: the DATA segment of an FCS file) to the
 // device as the bytes they hold.  Whole records travel in slabs - byte copies, no packing pass on the host whatever
 // src_cols / d is - and k_ingest_list (cc_ingest_list.h) swaps, gathers the selected channels, masks, widens, scales, checks and
 // writes both resident copies.  Here: the descriptor's check (list_check -> ListSrc, cc_ingest_src.h), the descriptors' way to
 // the device and the launches of k_ingest_list and k_col_minmax_list for a staged slab - with a transform (cc_list_transform,
 // checked by list_check_xf) those of k_ingest_list_xf and k_col_minmax_list_xf (cc_ingest_list_xf.h).  The upload, the prefetch and the column
 // reduction themselves are those of every staged source (cc_api_ingest.inc); cc_assign_list is in cc_api_assign.inc.
+// With logicle rows (cc_list_logicle, checked by list_check_lg; the coefficients from cc_logicle.h) the same two kernels run as
+// their logicle instances; cc_logicle_coefficients hands the coefficients out.
 // (included by cc_api.hip, the one translation unit, behind cc_api_views.inc)
 
 namespace {
@@ -102,11 +104,54 @@ int list_check_xf(cc_handle* h, const cc_list_transform* xf, ListSrc* out)
     return (int)CC_OK;
 }
 
-// list_check, then list_check_xf: what every `_list_xf` entry point begins with
-int list_check(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, bool need_points, ListSrc* out)
+// The logicle rows' refusals (cc_list_logicle), behind list_check_xf's and like them before anything is read, launched or
+// allocated; the coefficients (cc_logicle_derive: the one place they are computed) into `out` behind the cofactors.  lg null, or
+// every T == 0: no logicle scale - the `_list_xf` sibling, untouched.
+int list_check_lg(cc_handle* h, const cc_list_logicle* lg, ListSrc* out)
 {
-    const int rc = list_check(h, lm, need_points, out);
-    return rc != CC_OK ? rc : list_check_xf(h, xf, out);
+    if (!lg) return (int)CC_OK;
+    if (lg->reserved != 0) return fail(h, CC_ERR_BAD_ARG, "list logicle: reserved must be 0");
+    const int d = out->d, m = out->m;
+    if (lg->d != d)
+        return fail(h, CC_ERR_BAD_ARG, "list logicle: d is " + std::to_string(lg->d) + ", the list mode selects " + std::to_string(d));
+    if (!lg->twma) return fail(h, CC_ERR_BAD_ARG, "list logicle: twma is null with d > 0");
+    std::vector<double> coef((size_t)5 * d, 0.0);
+    bool on = false;
+    for (int c = 0; c < d; ++c) {
+        double k[8];
+        const double* row = lg->twma + (size_t)4 * c;
+        const char* why = cc_logicle_derive(row, k);
+        if (why) return fail(h, CC_ERR_BAD_ARG, "list logicle: dimension " + std::to_string(c) + ": " + why);
+        if (row[0] == 0.0) continue;
+        if (out->has_cof && out->xf_f[(size_t)m * m + c] > 0.0)
+            return fail(h, CC_ERR_BAD_ARG, "list logicle: dimension " + std::to_string(c) + " has a cofactor and a logicle scale");
+        on = true;
+        std::copy(k, k + 5, coef.begin() + (size_t)5 * c);
+    }
+    if (!on) return (int)CC_OK;
+    if (!out->xf) {  // (no transform beside it: none compensated, no cofactors)
+        out->xf = true;
+        out->m = 0;
+        out->xf_f.clear();
+        out->xf_i.assign((size_t)d, -1);
+    }
+    if (!out->has_cof) {
+        out->has_cof = true;
+        out->xf_f.insert(out->xf_f.end(), (size_t)d, 0.0);
+    }
+    out->lg = true;
+    out->lg_twma.assign(lg->twma, lg->twma + (size_t)4 * d);
+    out->xf_f.insert(out->xf_f.end(), coef.begin(), coef.end());
+    return (int)CC_OK;
+}
+
+// list_check, then list_check_xf, then list_check_lg: what every `_list_xl` entry point begins with
+int list_check(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg, bool need_points,
+               ListSrc* out)
+{
+    int rc = list_check(h, lm, need_points, out);
+    if (rc == CC_OK) rc = list_check_xf(h, xf, out);
+    return rc != CC_OK ? rc : list_check_lg(h, lg, out);
 }
 
 // the descriptors, and behind them the transform, into `dev` (ListSrc::desc_words() ints) on `st`
@@ -154,11 +199,11 @@ void ingest_list_launch(hipStream_t st, const void* raw, const ListSrc& v, const
         const cc_list_xf xf = list_xf_device(v, desc);
         with_list_dtype(v.dtype, [&](auto t) {
             using T = decltype(t);
-            with_bools([&](auto W) {
-                hipLaunchKernelGGL((k_ingest_list_xf<T, decltype(W)::value>), grid, dim3(256), 0, st,
+            with_bools([&](auto W, auto L) {
+                hipLaunchKernelGGL((k_ingest_list_xf<T, decltype(W)::value, decltype(L)::value>), grid, dim3(256), 0, st,
                                    static_cast<const unsigned char*>(raw), v.src_cols, (int)ns, (long long)s0, (long long)n_total, d,
                                    (int)xt_rows, reinterpret_cast<const cc_list_desc*>(desc), xf, X, Xt, scale, mn, bad);
-            }, v.swapped());
+            }, v.swapped(), v.lg);
         });
         return;
     }
@@ -180,12 +225,12 @@ void minmax_list_launch(hipStream_t st, const ListSrc& v, const void* raw, const
         const cc_list_xf xf = list_xf_device(v, desc);
         with_list_dtype(v.dtype, [&](auto t) {
             using T = decltype(t);
-            with_bools([&](auto W) {
-                hipLaunchKernelGGL((k_col_minmax_list_xf<T, decltype(W)::value>),
+            with_bools([&](auto W, auto L) {
+                hipLaunchKernelGGL((k_col_minmax_list_xf<T, decltype(W)::value, decltype(L)::value>),
                                    dim3(chunks, (d + CC_INGEST_TILE - 1) / CC_INGEST_TILE), dim3(256), 0, st,
                                    static_cast<const unsigned char*>(raw), (long long)ns, v.src_cols, d,
                                    reinterpret_cast<const cc_list_desc*>(desc), xf, part, chunks);
-            }, v.swapped());
+            }, v.swapped(), v.lg);
         });
         return;
     }
@@ -203,44 +248,75 @@ void minmax_list_launch(hipStream_t st, const ListSrc& v, const void* raw, const
 
 extern "C" {
 
-int cc_points_upload_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const double* scale,
-                             const double* min_)
+int cc_points_upload_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg,
+                             const double* scale, const double* min_)
 {
     if (!h) return CC_ERR_BAD_ARG;
     if ((scale == nullptr) != (min_ == nullptr)) return fail(h, CC_ERR_BAD_ARG, "list mode: scale and min_ go together");
     ListSrc v;
-    const int rc = list_check(h, lm, xf, false, &v);
+    const int rc = list_check(h, lm, xf, lg, false, &v);
     if (rc != CC_OK) return rc;
     return guarded(h, [&]() { return upload_source(h, IngestSrc::of(v), scale, min_); });
+}
+
+int cc_points_prefetch_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg,
+                               const double* scale, const double* min_)
+{
+    if (!h) return CC_ERR_BAD_ARG;
+    if ((scale == nullptr) != (min_ == nullptr)) return fail(h, CC_ERR_BAD_ARG, "list mode: scale and min_ go together");
+    ListSrc v;
+    const int rc = list_check(h, lm, xf, lg, true, &v);
+    if (rc != CC_OK) return rc;
+    return guarded(h, [&]() { return prefetch_source(h, IngestSrc::of(v), scale, min_); });
+}
+
+int cc_col_minmax_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg,
+                          double* out_min, double* out_max)
+{
+    if (!h || !out_min || !out_max) return CC_ERR_BAD_ARG;
+    ListSrc v;
+    const int rc = list_check(h, lm, xf, lg, true, &v);
+    if (rc != CC_OK) return rc;
+    return guarded(h, [&]() { return col_minmax_slabs(h, IngestSrc::of(v), out_min, out_max); });
+}
+
+int cc_online_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg, int64_t* out_uid,
+                      int8_t* out_path)
+{
+    int rc = cc_points_upload_list_xl(h, lm, xf, lg, nullptr, nullptr);
+    if (rc != CC_OK) return rc;
+    rc = cc_online_run(h);
+    if (rc != CC_OK) return rc;
+    return cc_labels_download(h, out_uid, out_path);
+}
+
+int cc_logicle_coefficients(const double twma[4], double out[8])
+{
+    if (!twma || !out) return CC_ERR_BAD_ARG;
+    return cc_logicle_derive(twma, out) ? (int)CC_ERR_BAD_ARG : (int)CC_OK;
+}
+
+// the `_list_xf` entry points: their `_xl` siblings without a logicle scale
+int cc_points_upload_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const double* scale,
+                             const double* min_)
+{
+    return cc_points_upload_list_xl(h, lm, xf, nullptr, scale, min_);
 }
 
 int cc_points_prefetch_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const double* scale,
                                const double* min_)
 {
-    if (!h) return CC_ERR_BAD_ARG;
-    if ((scale == nullptr) != (min_ == nullptr)) return fail(h, CC_ERR_BAD_ARG, "list mode: scale and min_ go together");
-    ListSrc v;
-    const int rc = list_check(h, lm, xf, true, &v);
-    if (rc != CC_OK) return rc;
-    return guarded(h, [&]() { return prefetch_source(h, IngestSrc::of(v), scale, min_); });
+    return cc_points_prefetch_list_xl(h, lm, xf, nullptr, scale, min_);
 }
 
 int cc_col_minmax_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, double* out_min, double* out_max)
 {
-    if (!h || !out_min || !out_max) return CC_ERR_BAD_ARG;
-    ListSrc v;
-    const int rc = list_check(h, lm, xf, true, &v);
-    if (rc != CC_OK) return rc;
-    return guarded(h, [&]() { return col_minmax_slabs(h, IngestSrc::of(v), out_min, out_max); });
+    return cc_col_minmax_list_xl(h, lm, xf, nullptr, out_min, out_max);
 }
 
 int cc_online_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, int64_t* out_uid, int8_t* out_path)
 {
-    int rc = cc_points_upload_list_xf(h, lm, xf, nullptr, nullptr);
-    if (rc != CC_OK) return rc;
-    rc = cc_online_run(h);
-    if (rc != CC_OK) return rc;
-    return cc_labels_download(h, out_uid, out_path);
+    return cc_online_list_xl(h, lm, xf, nullptr, out_uid, out_path);
 }
 
 // the `_list` entry points: their `_xf` siblings without a transform

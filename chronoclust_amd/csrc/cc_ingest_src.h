@@ -1,5 +1,5 @@
 // cc_ingest_src.h — what the host knows of points that reach the device through staging: IngestSrc, one description for
-// float32 rows (`_f32`), a checked cc_points_view (`_view`) and a checked cc_list_mode (`_list`, `_list_xf`), with float64 rows - a
+// float32 rows (`_f32`), a checked cc_points_view (`_view`) and a checked cc_list_mode (`_list`, `_list_xf`, `_list_xl`), with float64 rows - a
 // whole-array copy, not staged - as its fourth kind.  The upload, the prefetch and cc_assign (cc_api_ingest.inc,
 // cc_api_assign.inc) are written once against it; cc_handle::Prefetch keeps one to tell which upload may adopt it.
 // Host data only: the staging copies and the kernel launches per kind are in cc_api_ingest.inc.
@@ -33,9 +33,12 @@ struct ListSrc {
     // the transform of the `_list_xf` entry points (cc_list_transform, checked), a copy: xf_f = comp[m][m], then the d
     // cofactors where there are any; xf_i = the m compensated columns, their m masks, then per selected dimension its index
     // into them or -1 (cc_list_xf, cc_ingest_list_xf.h).  On the device both lie behind the descriptors: xf_words() more ints.
-    bool xf = false, has_cof = false;
+    // The logicle rows of the `_list_xl` entry points (cc_list_logicle, checked): lg_twma = the d rows T, W, M, A as given, kept
+    // for `same`; with one of them on (lg) the cofactors are always laid - zeros where none were given - and behind them, in
+    // xf_f too, the coefficients [d][5] the kernels read (cc_logicle.h).
+    bool xf = false, has_cof = false, lg = false;
     int m = 0;
-    std::vector<double> xf_f;
+    std::vector<double> xf_f, lg_twma;
     std::vector<int> xf_i;
     size_t xf_words() const { return xf ? 2 * xf_f.size() + xf_i.size() : 0; }
     size_t desc_words() const { return (size_t)2 * d + xf_words(); }
@@ -96,9 +99,11 @@ struct IngestSrc {
         if (list.dtype != o.list.dtype || list.src_cols != o.list.src_cols || list.flags != o.list.flags) return false;
         for (int i = 0; i < d; ++i)
             if (list.desc[i].col != o.list.desc[i].col || list.desc[i].mask != o.list.desc[i].mask) return false;
-        // the transform by content: m, the columns, the bits of every matrix entry and cofactor
+        // the transform by content: m, the columns, the bits of every matrix entry, cofactor and logicle row
         if (list.xf != o.list.xf || list.m != o.list.m || list.has_cof != o.list.has_cof || list.xf_i != o.list.xf_i ||
-            list.xf_f.size() != o.list.xf_f.size())
+            list.xf_f.size() != o.list.xf_f.size() || list.lg != o.list.lg || list.lg_twma.size() != o.list.lg_twma.size())
+            return false;
+        if (!list.lg_twma.empty() && memcmp(list.lg_twma.data(), o.list.lg_twma.data(), list.lg_twma.size() * sizeof(double)) != 0)
             return false;
         return list.xf_f.empty() || memcmp(list.xf_f.data(), o.list.xf_f.data(), list.xf_f.size() * sizeof(double)) == 0;
     }

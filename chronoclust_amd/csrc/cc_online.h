@@ -233,4 +233,5 @@ __device__ __forceinline__ double cc_sel_scale(unsigned mask, double scaled, dou
 #include "cc_points.h"    // transposed copy, finiteness check, scaler
 #include "cc_ingest.h"    // the fused ingest of a point view: any accepted element type, rows or columns
 #include "cc_ingest_list.h"  // ... and of list-mode event records: either byte order, a list of channels
+#include "cc_logicle.h"  // ... (the coefficients of the logicle scale, derived on the host)
 #include "cc_ingest_list_xf.h"  // ... and of event records that are compensated and arcsinh-transformed on the way

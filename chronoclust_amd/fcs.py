@@ -6,7 +6,8 @@ the device as they are: the byte swap, the selection of the channels, the `$PnR`
 (cc_points_upload_list).  Layouts the device route does not take are decoded on the host into a float64 array.
 With compensate / cofactor the file's own spillover matrix is inverted here and travels with the ListMode as a
 `_lib.ListTransform`: the compensation and arcsinh(x / cofactor) happen on the device too (cc_points_upload_list_xf);
-sidecar_transform reads the `<file>.transform` that asks for them beside a timepoint of app.run."""
+with logicle the channels of fluorescence flow cytometry take the logicle (biexponential) scale there instead, solved per value
+(cc_points_upload_list_xl); sidecar_transform reads the `<file>.transform` that asks for them beside a timepoint of app.run."""
 import numpy as np
 
 from ._lib import MAX_COMP, ListMode, ListTransform
@@ -205,6 +206,54 @@ def _cofactors(cofactor, picked):
     return out
 
 
+LOGICLE_KEYS = ("T", "W", "M", "A")
+LOGICLE_DEFAULTS = dict(W=0.5, M=4.5, A=0.0)  # (T: the channel's $PnR)
+
+
+def _is_logicle_row(spec):
+    """True for {"T": number, "W": ..., "M": ..., "A": ...}, every key optional: the parameters of one logicle scale."""
+    return isinstance(spec, dict) and set(spec) <= set(LOGICLE_KEYS) and \
+        all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in spec.values())
+
+
+def _is_logicle_spec(spec):
+    """True for the two forms `logicle` takes: one row for every channel, or {channel name: row}."""
+    return _is_logicle_row(spec) or (isinstance(spec, dict) and len(spec) > 0 and all(_is_logicle_row(v) for v in spec.values()))
+
+
+def _logicles(logicle, picked, sel, cof, text):
+    """[d, 4] rows T, W, M, A, one per selected channel (T == 0: off the scale), or None.  One row: every selected channel
+    without a cofactor; by name: the channels named - one that has a cofactor too is refused.  An omitted T is the channel's
+    $PnR, W 0.5, M 4.5, A 0."""
+    if logicle is None:
+        return None
+    if not _is_logicle_spec(logicle):
+        raise ValueError("FCS: logicle must be {T, W, M, A: number} (every key optional) or {channel name: such an object}")
+    by_name = not _is_logicle_row(logicle)
+    if by_name:
+        unknown = [k for k in logicle if k not in picked]
+        if unknown:
+            raise ValueError("FCS: logicle names %r, which is no selected channel (selected: %s)" % (unknown[0], ", ".join(picked)))
+    out = np.zeros((len(picked), 4), np.float64)
+    for k, name in enumerate(picked):
+        has_cof = cof is not None and cof[k] > 0
+        if by_name:
+            if name not in logicle:
+                continue
+            if has_cof:
+                raise ValueError("FCS: channel %s has a cofactor and a logicle scale: it takes one or the other" % name)
+            row = logicle[name]
+        elif has_cof:
+            continue
+        else:
+            row = logicle
+        T = float(row["T"]) if "T" in row else float(_need(text, "$P%dR" % (sel[k] + 1)))
+        out[k] = [T] + [float(row.get(key, LOGICLE_DEFAULTS[key])) for key in LOGICLE_KEYS[1:]]
+        if not out[k, 0] > 0 or not np.isfinite(out[k]).all():
+            raise ValueError("FCS: the logicle scale of channel %s needs a positive, finite T (%r) and finite W, M, A" % (name, T))
+    return out
+
+
 def _refuse_amplified(text, channels, names):
     """With a transform asked for, $PnE other than 0,0 and $PnG other than 1 stay unapplied - but no longer silently."""
     for c in channels:
@@ -228,7 +277,7 @@ def _refuse_amplified(text, channels, names):
                                  "compensation or cofactor" % (c + 1, g.strip(), names[c]))
 
 
-def read_fcs(path, columns=None, compensate=False, cofactor=None):
+def read_fcs(path, columns=None, compensate=False, cofactor=None, logicle=None):
     """(points, names, text) of a list-mode FCS file.
 
     points: the DATA segment as a `_lib.ListMode` over the memory-mapped file - nothing is decoded or copied on the host -
@@ -250,6 +299,12 @@ def read_fcs(path, columns=None, compensate=False, cofactor=None):
     takes the host route, the float64 array with the transform applied on the host; a selected or compensated channel whose
     $PnE is not 0,0 or whose $PnG is present and not 1 is a ValueError naming it, and so is a spillover keyword that is
     absent, malformed, names an unknown channel or holds a singular matrix.  Without either nothing changes.
+    logicle: the logicle (biexponential) scale of fluorescence flow cytometry (Moore and Parks 2012), after the compensation, on
+    the unit display scale (T maps to 1, 0 to (A + W) / (M + A)) - {"T": .., "W": .., "M": .., "A": ..} for every selected
+    channel that has no cofactor, or {channel name: {...}} per channel; an omitted T is the channel's $PnR, W 0.5, M 4.5, A 0.
+    A channel takes a cofactor or the logicle scale: one that is given both by name is a ValueError, as are parameters outside
+    T > 0, M > 0, 0 <= W, 2 W <= M, -W <= A <= M - 2 W.  $PnE and $PnG are refused as for a cofactor.  The scale is solved on
+    the device as the events land (cc_points_upload_list_xl), or on the host for a layout that takes the host route.
     ValueError naming the keyword for: $DATATYPE A, a $MODE other than L, a DATA segment shorter than $TOT * $PAR elements,
     channel widths that are no whole bytes, a malformed HEADER or TEXT."""
     mm = np.memmap(path, dtype=np.uint8, mode="c")  # (copy-on-write: the pages are the file's until somebody writes, nobody does)
@@ -301,11 +356,15 @@ def read_fcs(path, columns=None, compensate=False, cofactor=None):
     picked = [names[c] for c in sel]
     raw = mm[data_lo:data_lo + tot * event_bytes]
     transform = comp_idx = None
-    if compensate or cofactor is not None:
+    if compensate or cofactor is not None or logicle is not None:
         comp_idx, inv = _compensation(text, names) if compensate else ([], None)
         cof = _cofactors(cofactor, picked)
         _refuse_amplified(text, list(dict.fromkeys(sel + comp_idx)), names)
-        transform = ListTransform(comp_cols=comp_idx if compensate else None, comp=inv, cofactor=cof)
+        rows = _logicles(logicle, picked, sel, cof, text)
+        try:
+            transform = ListTransform(comp_cols=comp_idx if compensate else None, comp=inv, cofactor=cof, logicle=rows)
+        except ValueError as e:
+            raise ValueError("FCS: %s" % e) from None
     ascending, descending = order == sorted(order), order == sorted(order, reverse=True)
     uniform = len(set(widths)) == 1 and widths[0] in ((32,) if datatype == "F" else (64,) if datatype == "D" else (8, 16, 32))
     if uniform and (ascending or descending):
@@ -343,7 +402,9 @@ def sidecar_columns(path):
 
 def sidecar_transform(path):
     """The transform in `<file>.transform`, as keyword arguments of read_fcs, or None without that file.  The file is JSON:
-    {"compensate": bool, "cofactor": number | {channel name: number}}, either key optional."""
+    {"compensate": bool, "cofactor": number | {channel name: number}, "logicle": {"T": number, "W": .., "M": .., "A": ..} |
+    {channel name: {...}}}, every key optional (and every key of a logicle object: read_fcs has the defaults); the returned
+    dict carries "logicle" only where the file does."""
     import json
     import os
     name = str(path) + ".transform"
@@ -354,12 +415,17 @@ def sidecar_transform(path):
             spec = json.load(f)
         except ValueError as e:
             raise ValueError("%s: not JSON (%s)" % (name, e)) from None
-    if not isinstance(spec, dict) or set(spec) - {"compensate", "cofactor"}:
-        raise ValueError('%s: expected {"compensate": bool, "cofactor": number or {name: number}}' % name)
+    if not isinstance(spec, dict) or set(spec) - {"compensate", "cofactor", "logicle"} or \
+            ("logicle" in spec and not _is_logicle_spec(spec["logicle"])):
+        raise ValueError('%s: expected {"compensate": bool, "cofactor": number or {name: number}, "logicle": {T, W, M, A: number} '
+                         'or {name: {T, W, M, A: number}}}' % name)
     compensate, cofactor = spec.get("compensate", False), spec.get("cofactor")
     if not isinstance(compensate, bool):
         raise ValueError("%s: compensate must be true or false" % name)
     numbers = list(cofactor.values()) if isinstance(cofactor, dict) else [] if cofactor is None else [cofactor]
     if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in numbers):
         raise ValueError("%s: cofactor must be a number or an object of channel name: number" % name)
-    return dict(compensate=compensate, cofactor=cofactor)
+    out = dict(compensate=compensate, cofactor=cofactor)
+    if "logicle" in spec:
+        out["logicle"] = spec["logicle"]
+    return out

@@ -18,8 +18,9 @@ def read_timepoint(filename):
     back as a `_lib.ListMode` over the memory-mapped DATA segment - the device decodes it - or, for the layouts that route
     does not take, as a float64 array decoded on the host; `<file>.columns` (one name per line, matched against $PnN, then
     $PnS) selects and orders the channels, without it all channels are taken in file order; `<file>.transform` (JSON:
-    {"compensate": bool, "cofactor": number | {name: number}}, fcs.sidecar_transform) asks for the file's own spillover
-    compensation and arcsinh(x / cofactor), applied on the device as the events land (read_fcs)."""
+    {"compensate": bool, "cofactor": number | {name: number}, "logicle": {T, W, M, A} | {name: {T, W, M, A}}},
+    fcs.sidecar_transform) asks for the file's own spillover compensation and arcsinh(x / cofactor) or the logicle scale,
+    applied on the device as the events land (read_fcs)."""
     if str(filename).lower().endswith(".fcs"):
         from ..fcs import read_fcs, sidecar_columns, sidecar_transform
         return read_fcs(filename, columns=sidecar_columns(filename), **(sidecar_transform(filename) or {}))[0]

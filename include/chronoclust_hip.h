@@ -18,7 +18,9 @@
  *    list-mode event records as an FCS file holds them, either byte order, a
  *    list of channels -, decoded on the device; the `_list_xf` entry points: the
  *    same with a cc_list_transform - spillover compensation and
- *    asinh(x / cofactor) -, applied on the device as the events are decoded);
+ *    asinh(x / cofactor) -, applied on the device as the events are decoded; the
+ *    `_list_xl` entry points: the same with a cc_list_logicle - the logicle
+ *    display scale, solved per value on the device);
  *  - one handle = one HDDStream state on one GPU; a handle is not thread-safe;
  *  - all floating-point work is IEEE double, no FMA contraction, sums over
  *    dimensions strictly left to right, so results are bit-identical to the
@@ -377,6 +379,49 @@ int cc_col_minmax_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_tr
 int cc_online_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, int64_t* out_uid, int8_t* out_path);
 int cc_assign_list_xf(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, int64_t* out_uid, int8_t* out_path,
                       double* out_dist);
+
+/* List-mode event records on the logicle (biexponential) display scale, solved on the device: what fluorescence flow cytometry
+ * is clustered on, as arcsinh is the scale of mass cytometry.  The scale of Parks, Roederer and Moore 2006 in the
+ * parameterisation of Moore and Parks 2012; for one selected dimension with T > 0, M > 0, 0 <= W, 2 W <= M, -W <= A <= M - 2 W:
+ *   w  = W / (M + A)      x2 = A / (M + A)      x1 = x2 + w      x0 = x2 + 2 w      b = (M + A) ln 10
+ *   d  = the root in (0, b] of  2 (ln d - ln b) + w (d + b) = 0        (w == 0: d = b)
+ *   ca = exp(x0 (b + d))          mf = exp(b x1) - ca exp(-d x1)       a = T / ((exp(b) - mf) - ca exp(-d))
+ *   pa = a exp(b x1)              pc = a ca exp(-d x1)
+ *   G(u) = pa (exp(b u) - 1) - pc (exp(-d u) - 1),  u >= 0:  G(0) = 0, G(1 - x1) = T, G''(0) = 0, G' > 0
+ *   logicle(v) = x1 + sign(v) u,  u the root of G(u) = |v|;  logicle(+-0) = x1
+ * The result is on the UNIT display scale: T maps to 1 and 0 to x1, it is not multiplied by M; values beyond +-T map beyond
+ * [2 x1 - 1, 1] and are not clipped.  Per value: the decoding, then the compensation of the cc_list_transform (unchanged, bit
+ * for bit), then the logicle scale OR the cofactor - a dimension that carries both is refused -, then scale / min_, then the
+ * finiteness flag.  A finite v of any magnitude gives a finite result; the solve takes a fixed number of Halley steps, no loop
+ * depends on the data.  A NaN or Inf v gives a non-finite result and the upload is refused with CC_ERR_NONFINITE, as ever.
+ * There is no closed form: the result lies within a few units of np.spacing(max(|y|, 0.5)) of the root rounded once from
+ * extended precision (DESIGN.md sections 5.3 and 8: the measured distance) - where the very values matter, read them back
+ * (cc_points_download).
+ * The coefficients are derived once per dimension on the host - w, x2, x1, x0 as the doubles of the formulas, everything behind
+ * them in long double, rounded once - by the one function cc_logicle_coefficients also hands them out through:
+ * out = {x1, b, d, pa, pc, 0, 0, 0} (all zeros for T == 0), CC_ERR_BAD_ARG for parameters outside the contract.  It needs no
+ * handle and no GPU.
+ * Each `_list_xl` entry point is its `_list_xf` sibling with logicle rows; lg == NULL, or every T == 0, IS the sibling.  Refused
+ * with CC_ERR_BAD_ARG and a message that names the reason, before anything is read or launched, beside the siblings' refusals:
+ * d other than the cc_list_mode's, twma NULL, a parameter that is not finite, T < 0, on a row with T > 0: M <= 0, W < 0,
+ * 2 W > M, A < -W or A > M - 2 W (or coefficients beyond a double), a row with T > 0 on a dimension whose cofactor is > 0,
+ * reserved != 0.  A prefetch is adopted only by the upload with the same logicle rows, bit for bit. */
+typedef struct cc_list_logicle {
+    int32_t d;           /* selected dimensions: must equal the cc_list_mode's */
+    int32_t reserved;    /* 0 */
+    const double* twma;  /* [d][4] row-major: T, W, M, A; a row with T == 0 leaves the dimension off the logicle scale */
+} cc_list_logicle;
+int cc_points_upload_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg,
+                             const double* scale, const double* min_);
+int cc_points_prefetch_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg,
+                               const double* scale, const double* min_);
+int cc_col_minmax_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg,
+                          double* out_min, double* out_max);
+int cc_online_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg, int64_t* out_uid,
+                      int8_t* out_path);
+int cc_assign_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg, int64_t* out_uid,
+                      int8_t* out_path, double* out_dist);
+int cc_logicle_coefficients(const double twma[4], double out[8]);
 
 /* HDDStream.pcore_MC / outlier_MC (hddstream.py:56-57) in list order.
  * Any output pointer may be NULL.  cf1/cf2/cen/pref are [count, d]. */
