@@ -852,6 +852,9 @@ def check_online(case, res):
     elif kind == "arrivals":                                   # designed arrivals: tests/arrival_util.py
         import arrival_util
         arrival_util.check_arrivals(case, res)
+    elif kind == "seq-edge":                                   # the sequential kernels' capacity and hand-over edges: tests/seq_edge_util.py
+        import seq_edge_util
+        seq_edge_util.check_seq_edge(case, res)
     else:
         raise ValueError(kind)
 
@@ -860,6 +863,9 @@ def check_online(case, res):
 # wave (31 .. 33, 127 .. 129), one list empty, up to 4 096 rows; 1 to 2 048 points; every width at which the online phase
 # takes another kernel (3: k_seq_r; 5, 8: k_scan pads for itself; 13: padded rows; 14 .. 64: the ladder; 80, 200: k_seq_g and
 # its wide form).  The tables of 9 999 rows and more select forms by table size (see the tests that use them).
+# (This set is recorded by tests/golden/surface/online.npz and stays as it is.  Inputs designed for the sequential kernels' OWN
+# constants - k_seq_r's slots, k_seq's image and chunk, k_seq_g's stride, the host's chunk of 8 192 points - and the exact share of
+# each kernel: tests/seq_edge_util.py, SEQ_EDGE_CASES.)
 ONLINE_TABLES = {
     "victims-k4-16x14": (victims, dict(seed=101, pairs=16, d=14)),
     "victims-k4-300x16": (victims, dict(seed=102, pairs=300, d=16)),
