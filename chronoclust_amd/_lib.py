@@ -378,6 +378,54 @@ def logicle_host(v, twma):
     return out.reshape(v.shape)
 
 
+def _negq_sources(sources, want):
+    """(sources as a list, d, want as a uint8 mask [d] or None) of what negative_quantiles and its host sibling are given."""
+    sources = list(sources)
+    if not sources or not all(isinstance(s, ListMode) for s in sources):
+        raise ValueError("negative_quantiles: sources must be a non-empty list of ListMode")
+    d = sources[0].shape[1]
+    if any(s.shape[1] != d for s in sources):
+        raise ValueError("negative_quantiles: every source must select %d dimensions" % d)
+    if want is not None:
+        want = np.ascontiguousarray(np.asarray(want).astype(bool), dtype=np.uint8)
+        if want.shape != (d,):
+            raise ValueError("negative_quantiles: want must hold one entry per selected dimension")
+    return sources, d, want
+
+
+def compensation_only(source):
+    """The ListMode over the same records with the compensation of its transform and nothing else: no cofactors, no logicle
+    rows - what the negative quantiles are taken of."""
+    t = source.transform
+    if t is None or (source._cofactors is None and source._logicle is None):
+        return source
+    only = ListTransform(t.comp_cols, t.comp) if t.m else None
+    return ListMode(source.buffer, source.n, source.src_cols, source.dtype, columns=source.columns, masks=source.masks, transform=only)
+
+
+def negative_quantiles_host(sources, q=0.05, want=None):
+    """Handle.negative_quantiles on the host: (count, lo, hi, frac) from np.asarray of every source with its compensation only
+    (the device's sum, bit for bit), pooled - the route where there is no handle."""
+    sources, d, want = _negq_sources(sources, want)
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("negative_quantiles: q must be in [0, 1]")
+    vals = [np.asarray(compensation_only(s), dtype=np.float64) for s in sources]
+    count = np.full(d, -1, np.int64)
+    lo, hi, frac = np.zeros(d), np.zeros(d), np.zeros(d)
+    for c in range(d):
+        if want is not None and not want[c]:
+            continue
+        col = np.concatenate([v[:, c] for v in vals])
+        neg = np.sort(col[col < 0])
+        count[c] = neg.size
+        if neg.size:
+            h = np.float64(neg.size - 1) * np.float64(q)
+            j = int(np.floor(h))
+            lo[c], hi[c], frac[c] = neg[j], neg[min(j + 1, neg.size - 1)], h - np.floor(h)
+    return count, lo, hi, frac
+
+
 class CcRelaxedStats(C.Structure):
     _fields_ = [("super_steps", C.c_int64), ("minibatch_points", C.c_int64), ("deferred_points", C.c_int64),
                 ("reserved", C.c_int64 * 5)]
@@ -442,6 +490,10 @@ SYMBOLS = {
     "cc_online_list_xl": (C.c_int, [C.c_void_p, _lp, _xp, _gp, _i64p, _i8p]),
     "cc_assign_list_xl": (C.c_int, [C.c_void_p, _lp, _xp, _gp, _i64p, _i8p, _dp]),
     "cc_logicle_coefficients": (C.c_int, [_dp, _dp]),
+    "cc_negq_begin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int64]),
+    "cc_negq_add_list": (C.c_int, [C.c_void_p, _lp, _xp]),
+    "cc_negq_select": (C.c_int, [C.c_void_p, C.c_double, _i64p, _dp, _dp, _dp]),
+    "cc_negq_end": (C.c_int, [C.c_void_p]),
     "cc_count": (C.c_int, [C.c_void_p, C.c_int]),
     "cc_dim": (C.c_int, [C.c_void_p]),
     "cc_counters": (C.c_int, [C.c_void_p, _i64p, _i64p]),
@@ -869,6 +921,33 @@ class Handle(object):
         mx = np.empty(d, dtype=np.float64)
         self._ingest("col_minmax", kind, *(args + (_ptr(mn), _ptr(mx))))
         return mn, mx
+
+    def negative_quantiles(self, sources, q=0.05, want=None):
+        """(count, lo, hi, frac), each [d]: per selected dimension the exact order statistics around quantile q of the NEGATIVE
+        compensated values of `sources` - a list of ListMode of one width, pooled; each carries its own compensation in its
+        ListTransform, whose cofactors and logicle rows are ignored -, selected on the device (cc_negq_begin / _add_list /
+        _select / _end).  count = the negative values (NaN, +-0 and positive values are none; -Inf is), h = (count - 1) * q,
+        j = floor(h), frac = h - j, lo = sorted[j], hi = sorted[min(j + 1, count - 1)], bit for bit; count == 0: zeros.
+        np.quantile(np.array([lo, hi]), frac) is np.quantile of the negative values at q.  want: a mask [d] of the dimensions to
+        select (None: all); the others come back with count -1 and zeros.  Nothing else of the handle changes."""
+        sources, d, want = _negq_sources(sources, want)
+        count = np.empty(d, np.int64)
+        lo, hi, frac = np.empty(d), np.empty(d), np.empty(d)
+        self._check(self._lib.cc_negq_begin(self._h, d, _ptr(want, C.POINTER(C.c_uint8)), sum(s.n for s in sources)))
+        try:
+            for s in sources:
+                if s.n == 0:
+                    continue  # (an empty DATA segment has no address to describe)
+                desc, t = s.descriptor(), s.transform
+                xf = None
+                if t is not None and t.m:
+                    xf = C.byref(CcListTransform(t.m, 0, t.comp_cols.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 t.comp.ctypes.data_as(C.POINTER(C.c_double)), None))
+                self._check(self._lib.cc_negq_add_list(self._h, C.byref(desc), xf))
+            self._check(self._lib.cc_negq_select(self._h, float(q), _ptr(count, _i64p), _ptr(lo), _ptr(hi), _ptr(frac)))
+        finally:
+            self._lib.cc_negq_end(self._h)
+        return count, lo, hi, frac
 
     def points_download(self, d, scale=None, min_=None):
         """The resident points; with scale / min_, (X - min_) / scale (MinMaxScaler.inverse_transform)."""

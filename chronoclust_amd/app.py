@@ -36,6 +36,11 @@ def run(data, output_directory, gating_centroid_file=None, normalise_data=True, 
     completed timepoint (app.py:107-114, 165-166).  Unlike the reference's pickles (which lose the id counters
     and whose restart truncates result.csv) the images here hold the microcluster tables
     and counters, and result.csv is appended to.
+
+    `.fcs` timepoints whose `<file>.transform` holds a logicle row with "W": "estimate" (fcs.sidecar_transform): the width is
+    resolved once, before the scaler's fit - per channel name, pooled over all those timepoints, the quantile of the negative
+    compensated values selected on the device (fcs.estimate_sidecars) -, logged, and written to `<output_directory>/logicle.json`
+    (only then); a resumed run resolves again from the same files and gets the same bits.
     """
     program_state_dir = '{}/program_images'.format(output_directory)
     logger = setup_logger('{}/logs'.format(output_directory))
@@ -73,10 +78,21 @@ def run(data, output_directory, gating_centroid_file=None, normalise_data=True, 
     else:
         write_file_header(result_filename, result_file_header)
 
+    # `.fcs` timepoints whose sidecar holds "W": "estimate": one logicle width per channel, pooled over all of them and selected
+    # on the device, before anything is scaled (a resumed run resolves again from the same files: the same bits)
+    from .fcs import estimate_sidecars
+    logicle, resolved = estimate_sidecars(data, handle=hddstream._h)
+    if resolved:
+        import json
+        for name in sorted(resolved):
+            logger.info("Logicle scale of channel {} estimated from the events: {}".format(name, resolved[name]))
+        with open(f'{output_directory}/logicle.json', 'w') as f:
+            json.dump(resolved, f, indent=1, sort_keys=True)
+
     scaler = None
     if normalise_data:
         logger.info("Setting up scaler")
-        scaler = Scaler(data, handle=hddstream._h)  # column min / max reduced on the device, files parsed once
+        scaler = Scaler(data, handle=hddstream._h, logicle=logicle)  # column min / max reduced on the device, files parsed once
 
     import time
     del LAST_RUN_TIMINGS[:]
@@ -88,7 +104,7 @@ def run(data, output_directory, gating_centroid_file=None, normalise_data=True, 
         t0 = time.perf_counter()
         raw = scaler.parsed.pop(data_file, None) if scaler is not None else None
         if raw is None:
-            raw = read_timepoint(data_file)
+            raw = read_timepoint(data_file, logicle)
         tm["read"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         if normalise_data:

@@ -393,6 +393,7 @@ Rows padded_rows(cc_handle* h, hipStream_t st, Rows rows, int q, int round, int 
 #include "cc_api_views.inc"
 #include "cc_api_list.inc"
 #include "cc_api_ingest.inc"
+#include "cc_api_negq.inc"
 #include "cc_api_offline.inc"
 #include "cc_api_comm.inc"
 #include "cc_api_assign.inc"

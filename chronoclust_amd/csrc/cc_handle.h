@@ -326,6 +326,19 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
     long long list_points = 0;    // cc_list_points: events taken through the `_list` entry points since cc_create (ingest_raw again)
     DevBuf<int> list_desc;        // ... their descriptors {source column, mask} on the device, uploaded once per call (k_ingest_list)
 
+    // cc_negq_begin .. cc_negq_end: the pooled selection of negative compensated values (cc_negq.h, cc_api_negq.inc); scratch
+    // of its own, freed by cc_negq_end and with the handle, left alone by cc_reset
+    struct NegQ {
+        bool open = false;
+        int d = 0, nw = 0;            // selected dimensions of every source / how many of them are wanted
+        long long cap = 0, n = 0;     // events to come, pooled / events added so far
+        std::vector<int> wmap;        // [d] the row of `val` a selected dimension has, -1: not wanted
+        DevBuf<int> wdev;             // ... on the device
+        DevBuf<double> val;           // [nw][cap] the values, dimension-major
+        DevBuf<unsigned> hist;        // [nw][chunks][256] a pass's digit counts per chunk
+        DevBuf<unsigned long long> st, nxt, out;  // [nw][CC_NEGQ_STATE] / [nw][chunks] successor candidates / [nw][4] the results
+    } nq;
+
     // cc_points_prefetch: the next timepoint's points, uploaded by a worker thread through page-locked staging
     struct Prefetch {
         std::thread worker;

@@ -7,7 +7,9 @@ the device as they are: the byte swap, the selection of the channels, the `$PnR`
 With compensate / cofactor the file's own spillover matrix is inverted here and travels with the ListMode as a
 `_lib.ListTransform`: the compensation and arcsinh(x / cofactor) happen on the device too (cc_points_upload_list_xf);
 with logicle the channels of fluorescence flow cytometry take the logicle (biexponential) scale there instead, solved per value
-(cc_points_upload_list_xl); sidecar_transform reads the `<file>.transform` that asks for them beside a timepoint of app.run."""
+(cc_points_upload_list_xl); sidecar_transform reads the `<file>.transform` that asks for them beside a timepoint of app.run.
+estimate_logicle takes the width W of that scale from the events - the 5th percentile of a channel's negative compensated values,
+pooled over the files of a series and selected on the device (Handle.negative_quantiles) -, estimate_sidecars for a whole run."""
 import numpy as np
 
 from ._lib import MAX_COMP, ListMode, ListTransform
@@ -210,10 +212,23 @@ LOGICLE_KEYS = ("T", "W", "M", "A")
 LOGICLE_DEFAULTS = dict(W=0.5, M=4.5, A=0.0)  # (T: the channel's $PnR)
 
 
+ESTIMATE = "estimate"  # a row's W that estimate_logicle resolves from the events
+
+
 def _is_logicle_row(spec):
-    """True for {"T": number, "W": ..., "M": ..., "A": ...}, every key optional: the parameters of one logicle scale."""
-    return isinstance(spec, dict) and set(spec) <= set(LOGICLE_KEYS) and \
-        all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in spec.values())
+    """True for {"T": number, "W": ..., "M": ..., "A": ...}, every key optional: the parameters of one logicle scale.  W may be
+    the string "estimate" - the width is then taken from the events (estimate_logicle) -, and only beside it "q": number, the
+    quantile of the negative values it is taken at."""
+    if not isinstance(spec, dict) or not set(spec) <= set(LOGICLE_KEYS) | {"q"}:
+        return False
+    unresolved = _is_unresolved(spec)
+    if "q" in spec and not unresolved:
+        return False
+    return all((isinstance(v, (int, float)) and not isinstance(v, bool)) or (k == "W" and unresolved) for k, v in spec.items())
+
+
+def _is_unresolved(row):
+    return isinstance(row.get("W"), str) and row["W"] == ESTIMATE
 
 
 def _is_logicle_spec(spec):
@@ -247,6 +262,9 @@ def _logicles(logicle, picked, sel, cof, text):
             continue
         else:
             row = logicle
+        if _is_unresolved(row):
+            raise ValueError('FCS: the logicle scale of channel %s has "W": "estimate": read_fcs does not look at the events - '
+                             "resolve the width with estimate_logicle first (over every file of the series) and pass its rows" % name)
         T = float(row["T"]) if "T" in row else float(_need(text, "$P%dR" % (sel[k] + 1)))
         out[k] = [T] + [float(row.get(key, LOGICLE_DEFAULTS[key])) for key in LOGICLE_KEYS[1:]]
         if not out[k, 0] > 0 or not np.isfinite(out[k]).all():
@@ -305,6 +323,8 @@ def read_fcs(path, columns=None, compensate=False, cofactor=None, logicle=None):
     A channel takes a cofactor or the logicle scale: one that is given both by name is a ValueError, as are parameters outside
     T > 0, M > 0, 0 <= W, 2 W <= M, -W <= A <= M - 2 W.  $PnE and $PnG are refused as for a cofactor.  The scale is solved on
     the device as the events land (cc_points_upload_list_xl), or on the host for a layout that takes the host route.
+    A row whose W is "estimate" is a ValueError that names estimate_logicle: this function never looks at the events, and the
+    width of a series is one number over all its files - resolve it there and pass the rows it returns.
     ValueError naming the keyword for: $DATATYPE A, a $MODE other than L, a DATA segment shorter than $TOT * $PAR elements,
     channel widths that are no whole bytes, a malformed HEADER or TEXT."""
     mm = np.memmap(path, dtype=np.uint8, mode="c")  # (copy-on-write: the pages are the file's until somebody writes, nobody does)
@@ -404,7 +424,8 @@ def sidecar_transform(path):
     """The transform in `<file>.transform`, as keyword arguments of read_fcs, or None without that file.  The file is JSON:
     {"compensate": bool, "cofactor": number | {channel name: number}, "logicle": {"T": number, "W": .., "M": .., "A": ..} |
     {channel name: {...}}}, every key optional (and every key of a logicle object: read_fcs has the defaults); the returned
-    dict carries "logicle" only where the file does."""
+    dict carries "logicle" only where the file does.  A logicle object's W may be "estimate", with an optional "q" beside it:
+    the width is then taken from the events of the whole run (estimate_sidecars, which app.run calls)."""
     import json
     import os
     name = str(path) + ".transform"
@@ -429,3 +450,140 @@ def sidecar_transform(path):
     if "logicle" in spec:
         out["logicle"] = spec["logicle"]
     return out
+
+
+def logicle_w(count, lo, hi, frac, T, M):
+    """The logicle width of Parks, Roederer and Moore 2006 from the order statistics of a channel's negative compensated values
+    (Handle.negative_quantiles): r = numpy's linear interpolation of (lo, hi) at frac - np.quantile of the negative values -,
+    W = (M - log10(T / |r|)) / 2 clamped to [0, M / 2]; 0 where there is no negative value (count == 0).  ValueError where r
+    is -Inf."""
+    if int(count) == 0:
+        return 0.0
+    with np.errstate(all="ignore"):
+        r = np.quantile(np.array([lo, hi], np.float64), np.float64(frac))
+        if np.isinf(lo) or not np.isfinite(r):
+            raise ValueError("the quantile of the negative values is not finite (%r)" % float(lo))
+        T, M = np.float64(T), np.float64(M)
+        W = (M - np.log10(T / np.abs(r))) / 2
+    return float(min(max(W, np.float64(0.0)), M / 2))
+
+
+def _channels(text, columns):
+    """(indices, $PnN of all channels) of the channels read_fcs takes for `columns`."""
+    par = _int(text, "$PAR")
+    names = [text.get("$P%dN" % (i + 1), "P%d" % (i + 1)).strip() for i in range(par)]
+    stains = [text.get("$P%dS" % (i + 1), "").strip() for i in range(par)]
+    return _select(columns, names, stains), names
+
+
+def estimate_logicle(paths, columns=None, compensate=False, logicle=None, q=0.05, handle=None):
+    """{channel name: {"T": .., "W": .., "M": .., "A": ..}}: the rows of `logicle` (read_fcs's two forms: one row for every
+    selected channel, or {channel name: row}) resolved over the files `paths`, POOLED - a time series takes one W per channel
+    over all its timepoints.  A row whose W is "estimate" gets W = (M - log10(T / |r|)) / 2, clamped to [0, M / 2], r the
+    quantile q (the row's own "q", else `q`: 0.05) of the channel's NEGATIVE values after compensation - no negative value:
+    W = 0 -; a row with a numeric W passes through with the defaults filled in (T: the channel's $PnR, M 4.5, A 0).
+    handle: a `_lib.Handle` - the events stream through its staging and the order statistics are selected on the device
+    (Handle.negative_quantiles), nothing is decoded on the host; None: the same answer on the host, bit for bit.  Files of the
+    layouts read_fcs decodes on the host are handed on as native float64 records and pool with the rest.
+    ValueError where the files disagree on a channel's T, M or A or on the channels themselves, where a named channel is
+    missing from a file, for $PnE / $PnG as in read_fcs, for q outside [0, 1], for a quantile of -Inf (naming the channel) and
+    for a resolved row outside the logicle scale's contract."""
+    from . import _lib
+    if logicle is None or not _is_logicle_spec(logicle):
+        raise ValueError('FCS: logicle must be {T, W, M, A: number, W may be "estimate"} or {channel name: such an object}')
+    paths = list(paths)
+    if not paths:
+        raise ValueError("FCS: estimate_logicle needs at least one file")
+    by_name = not _is_logicle_row(logicle)
+    sources, first, first_picked = [], None, None
+    for path in paths:
+        points, picked, text = read_fcs(path, columns=columns, compensate=compensate)
+        sel, names = _channels(text, columns)
+        _refuse_amplified(text, sel, names)
+        if first_picked is None:
+            first_picked = picked
+        elif picked != first_picked:
+            raise ValueError("FCS: %s holds the channels %s, the files before it %s" % (path, ", ".join(picked), ", ".join(first_picked)))
+        if by_name:
+            unknown = [k for k in logicle if k not in picked]
+            if unknown:
+                raise ValueError("FCS: logicle names %r, which is no selected channel of %s (selected: %s)"
+                                 % (unknown[0], path, ", ".join(picked)))
+        rows = {}
+        for k, name in enumerate(picked):
+            row = logicle.get(name) if by_name else logicle
+            if row is None:
+                continue
+            T = float(row["T"]) if "T" in row else float(_need(text, "$P%dR" % (sel[k] + 1)))
+            W = row.get("W", LOGICLE_DEFAULTS["W"])
+            rows[name] = dict(T=T, W=W if _is_unresolved(row) else float(W), M=float(row.get("M", LOGICLE_DEFAULTS["M"])),
+                              A=float(row.get("A", LOGICLE_DEFAULTS["A"])), q=float(row.get("q", q)), k=k)
+            if not 0.0 <= rows[name]["q"] <= 1.0:
+                raise ValueError("FCS: the quantile of channel %s must be in [0, 1] (%r)" % (name, rows[name]["q"]))
+        if first is None:
+            first = rows
+        for name, row in rows.items():
+            for key in ("T", "M", "A"):
+                if row[key] != first[name][key]:
+                    raise ValueError("FCS: %s gives channel %s the logicle %s %r, the files before it %r: a series takes one scale"
+                                     % (path, name, key, row[key], first[name][key]))
+        if not isinstance(points, ListMode):
+            points = ListMode(np.ascontiguousarray(points, dtype=np.float64), points.shape[0], points.shape[1], np.float64)
+        sources.append(points)
+    d = len(first_picked)
+    for qq in sorted(set(row["q"] for row in first.values() if row["W"] == ESTIMATE)):
+        want = np.zeros(d, bool)
+        for row in first.values():
+            want[row["k"]] |= row["W"] == ESTIMATE and row["q"] == qq
+        if handle is not None:
+            count, lo, hi, frac = handle.negative_quantiles(sources, qq, want)
+        else:
+            count, lo, hi, frac = _lib.negative_quantiles_host(sources, qq, want)
+        for name, row in first.items():
+            k = row["k"]
+            if want[k] and row["W"] == ESTIMATE:
+                try:
+                    row["W"] = logicle_w(count[k], lo[k], hi[k], frac[k], row["T"], row["M"])
+                except ValueError as e:
+                    raise ValueError("FCS: channel %s: %s" % (name, e)) from None
+    out = {}
+    for name, row in first.items():
+        out[name] = {key: row[key] for key in LOGICLE_KEYS}
+        try:
+            _lib.logicle_coefficients([out[name][key] for key in LOGICLE_KEYS])
+        except ValueError as e:
+            raise ValueError("FCS: channel %s: %s" % (name, e)) from None
+    return out
+
+
+def estimate_sidecars(paths, handle=None):
+    """({path: resolved logicle rows by channel name}, {channel name: row}) for the `.fcs` files among `paths` whose
+    `<file>.transform` holds a logicle row with "W": "estimate": estimate_logicle over all of them, pooled (files whose
+    sidecars ask for the same channels, compensation and rows are one pool).  The first result is what read_timepoint and
+    Scaler take as `logicle`; both are empty where no sidecar asks for an estimate."""
+    import json
+    groups = {}
+    for path in paths:
+        if not str(path).lower().endswith(".fcs"):
+            continue
+        kw = sidecar_transform(path)
+        spec = (kw or {}).get("logicle")
+        if spec is None or not any(_is_unresolved(row) for row in ([spec] if _is_logicle_row(spec) else spec.values())):
+            continue
+        columns = sidecar_columns(path)
+        if _is_logicle_row(spec):
+            # one row for every selected channel that has no cofactor, spelled by name
+            picked = read_fcs(path, columns=columns)[1]
+            cof = _cofactors(kw.get("cofactor"), picked)
+            spec = {name: spec for k, name in enumerate(picked) if cof is None or not cof[k] > 0}
+        key = json.dumps([columns, kw["compensate"], spec], sort_keys=True)
+        groups.setdefault(key, (columns, kw["compensate"], spec, []))[3].append(path)
+    overrides, resolved = {}, {}
+    for columns, compensate, spec, members in groups.values():
+        rows = estimate_logicle(members, columns=columns, compensate=compensate, logicle=spec, handle=handle)
+        for name, row in rows.items():
+            if resolved.setdefault(name, row) != row:
+                raise ValueError("FCS: the sidecars of this run give channel %s two logicle scales (%r, %r)" % (name, resolved[name], row))
+        for path in members:
+            overrides[path] = rows
+    return overrides, resolved

@@ -11,7 +11,7 @@ import pandas as pd
 from .._lib import ListMode, points_source
 
 
-def read_timepoint(filename):
+def read_timepoint(filename, logicle=None):
     """One timepoint as float64 [N, d].  CSV with a header row as in the reference (app.py:170, scaler.py:31);
     `.npy` files (binary side input: no text parse) are taken as they are - a float32 file stays float32 (cytometry events are
     single precision at the source; the device widens them), anything else becomes float64.  `.fcs` files (fcs.read_fcs) come
@@ -20,10 +20,14 @@ def read_timepoint(filename):
     $PnS) selects and orders the channels, without it all channels are taken in file order; `<file>.transform` (JSON:
     {"compensate": bool, "cofactor": number | {name: number}, "logicle": {T, W, M, A} | {name: {T, W, M, A}}},
     fcs.sidecar_transform) asks for the file's own spillover compensation and arcsinh(x / cofactor) or the logicle scale,
-    applied on the device as the events land (read_fcs)."""
+    applied on the device as the events land (read_fcs).  logicle: {path: logicle rows by channel name} - the rows that take
+    the place of the sidecar's for that file: what fcs.estimate_sidecars resolved where a sidecar holds "W": "estimate"."""
     if str(filename).lower().endswith(".fcs"):
         from ..fcs import read_fcs, sidecar_columns, sidecar_transform
-        return read_fcs(filename, columns=sidecar_columns(filename), **(sidecar_transform(filename) or {}))[0]
+        kw = sidecar_transform(filename) or {}
+        if logicle and filename in logicle:
+            kw = dict(kw, logicle=logicle[filename])
+        return read_fcs(filename, columns=sidecar_columns(filename), **kw)[0]
     if str(filename).endswith(".npy"):
         X = np.load(filename)
         return np.ascontiguousarray(X, dtype=np.float32 if X.dtype == np.float32 else np.float64)
@@ -31,9 +35,10 @@ def read_timepoint(filename):
 
 
 class Scaler(object):
-    def __init__(self, data_files=None, handle=None):
+    def __init__(self, data_files=None, handle=None, logicle=None):
         """handle: a chronoclust_amd._lib.Handle.  With it the fit reduces every file's columns on the device
-        (cc_col_minmax) and the parsed files are kept for the run, so that no file is parsed twice."""
+        (cc_col_minmax) and the parsed files are kept for the run, so that no file is parsed twice.
+        logicle: read_timepoint's {path: resolved logicle rows}, handed on to it."""
         self.scale_ = None
         self.min_ = None
         self.input_data = []
@@ -44,7 +49,7 @@ class Scaler(object):
             for filename in data_files:
                 # (kept as parsed where the library reads it where it lies - pandas hands a CSV out column-major -, else as
                 # a C-contiguous float64 copy)
-                X = read_timepoint(filename)
+                X = read_timepoint(filename, logicle)
                 if not isinstance(X, ListMode):  # (event records of an FCS file: the handle reads them where they lie)
                     X = points_source(X)[0]
                 self.parsed[filename] = X
@@ -57,7 +62,7 @@ class Scaler(object):
         elif data_files is not None:
             rows = []
             for filename in data_files:
-                rows.append(np.asarray(read_timepoint(filename)))
+                rows.append(np.asarray(read_timepoint(filename, logicle)))
             self.fit_scaler(np.concatenate(rows, axis=0) if rows else np.empty((0, 0)))
 
     def _finish_fit(self, data_min, data_max):

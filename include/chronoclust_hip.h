@@ -423,6 +423,35 @@ int cc_assign_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transf
                       int8_t* out_path, double* out_dist);
 int cc_logicle_coefficients(const double twma[4], double out[8]);
 
+/* An exact order statistic per selected column over the NEGATIVE compensated values of list-mode events, pooled over any number
+ * of sources and selected on the device: what the rule of Parks, Roederer and Moore 2006 takes the logicle width from
+ * (W = (M - log10(T / |r|)) / 2, r the 5th percentile of a channel's negative values - the caller's arithmetic).
+ * For one selected dimension, over every event added since cc_negq_begin:
+ *   v      the value the `_list_xf` entry points compute with cofactor 0 - decoded, masked, compensated by the source's own
+ *          comp (the same left-to-right sum, bit for bit) -, not put through a cofactor or a logicle scale, not scaled
+ *   neg    the multiset of all v < 0 (NaN, +-0 and positive values are not in it; -Inf is);  cnt = |neg|
+ *   h = (cnt - 1) * q in double;  j = floor(h);  frac = h - j
+ *   lo = sorted(neg)[j],  hi = sorted(neg)[min(j + 1, cnt - 1)]: exact order statistics, bit for bit
+ * cnt == 0 gives cnt = 0, lo = hi = frac = 0.  numpy's linear interpolation of (lo, hi) at frac is np.quantile(neg, q).
+ * cc_negq_begin: d selected dimensions per source, want[d] non-zero for the dimensions to select (NULL: all), capacity = the
+ * events to come, pooled; allocates want x capacity doubles of scratch (CC_ERR_OOM leaves the handle as it was); a begin while
+ * one is open starts over.  cc_negq_add_list: appends one source's events, streamed through the upload's staging buffers in the
+ * upload's slabs; xf as for cc_col_minmax_list_xf (NULL: no compensation) but its cofactors are not applied; any number of
+ * calls, n == 0 adds nothing.  cc_negq_select: cnt, lo, hi, frac per selected dimension (each [d]; a dimension that is not
+ * wanted: cnt = -1 and zeros) for one q in [0, 1]; any number of calls, nothing changes.  A radix select over the bit
+ * patterns, 8 passes of 8 bits: the number of launches and every loop's trip count are functions of the sizes alone, one host
+ * wait ends the call.  cc_negq_end frees the scratch; cc_destroy does too, cc_reset leaves it alone.
+ * Refused with CC_ERR_BAD_ARG and a message that names the reason, before anything is read, launched or allocated: a null
+ * handle or null outputs, d outside 1..CC_MAX_DIM, capacity < 0, add / select / end without begin, a cc_list_mode whose d is
+ * not begin's, a running total beyond capacity, q outside [0, 1] or NaN, and everything cc_col_minmax_list_xf refuses about lm
+ * and xf.  None of these calls changes what a later call can observe: resident points and labels, tables, counters,
+ * cc_list_points, a pending prefetch and cc_stats stay as they are.  They are not collective: in a group every rank that
+ * makes them gets the same answer. */
+int cc_negq_begin(cc_handle* h, int32_t d, const uint8_t* want, int64_t capacity);
+int cc_negq_add_list(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf);
+int cc_negq_select(cc_handle* h, double q, int64_t* out_count, double* out_lo, double* out_hi, double* out_frac);
+int cc_negq_end(cc_handle* h);
+
 /* HDDStream.pcore_MC / outlier_MC (hddstream.py:56-57) in list order.
  * Any output pointer may be NULL.  cf1/cf2/cen/pref are [count, d]. */
 int cc_count(cc_handle* h, int kind);
