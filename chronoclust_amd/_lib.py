@@ -244,18 +244,7 @@ class ListMode(object):
                 raise ValueError("ListMode: one mask per selected column")
         self.shape = (n, int(self.columns.size))
         self.transform = transform
-        self._cofactors = self._logicle = None
-        if transform is not None:
-            if not isinstance(transform, ListTransform):
-                raise ValueError("ListMode: transform must be a ListTransform")
-            self._cofactors = transform.cofactors(self.shape[1])
-            self._logicle = transform.logicles(self.shape[1])
-            if self._logicle is not None and not (self._logicle[:, 0] != 0).any():
-                self._logicle = None  # (every row off: the `_list_xf` sibling)
-            if self._logicle is not None and self._cofactors is not None:
-                both = np.flatnonzero((self._logicle[:, 0] != 0) & (self._cofactors > 0))
-                if both.size:
-                    raise ValueError("ListMode: dimension %d has a cofactor and a logicle scale" % both[0])
+        self._cofactors, self._logicle = _transform_rows(transform, self.shape[1], "ListMode")
 
     def __len__(self):
         return self.n
@@ -306,24 +295,97 @@ class ListMode(object):
             if self.masks is not None and c in cols:
                 x = x & self.masks[cols.index(c)].astype(native)
             xs.append(x.astype(np.float64))
-        for k, c in enumerate(cols):
-            hit = np.flatnonzero(t.comp_cols == c)
-            if hit.size:
-                i = int(hit[0])
-                v = xs[0] * t.comp[0, i]
-                for j in range(1, t.m):
-                    v = v + xs[j] * t.comp[j, i]
-                out[:, k] = v
-        if self._cofactors is not None:
-            with np.errstate(all="ignore"):
-                for k, cf in enumerate(self._cofactors.tolist()):
-                    if cf > 0:
-                        out[:, k] = np.arcsinh(out[:, k] / cf)
-        if self._logicle is not None:
-            for k, row in enumerate(self._logicle):
-                if row[0] != 0:
-                    out[:, k] = logicle_host(out[:, k], row)
-        return out
+        hits = [np.flatnonzero(t.comp_cols == c) for c in cols]
+        return _host_transform(out, xs, [int(h[0]) if h.size else -1 for h in hits], t, self._cofactors, self._logicle)
+
+
+def _transform_rows(transform, d, who):
+    """(cofactors [d] or None, logicle rows [d, 4] or None: every row off is none) of a ListTransform over d dimensions, with
+    the refusal of a dimension that carries a cofactor and a logicle scale - what ListMode and TransformedPoints (`who`) keep."""
+    if transform is None:
+        return None, None
+    if not isinstance(transform, ListTransform):
+        raise ValueError("%s: transform must be a ListTransform" % who)
+    cofactors = transform.cofactors(d)
+    logicle = transform.logicles(d)
+    if logicle is not None and not (logicle[:, 0] != 0).any():
+        logicle = None  # (every row off: the sibling without logicle rows)
+    if logicle is not None and cofactors is not None:
+        both = np.flatnonzero((logicle[:, 0] != 0) & (cofactors > 0))
+        if both.size:
+            raise ValueError("%s: dimension %d has a cofactor and a logicle scale" % (who, both[0]))
+    return cofactors, logicle
+
+
+def _host_transform(out, xs, hits, t, cofactors, logicle):
+    """The transform on the host over out [n, d] float64, the dimensions' own values, in place: xs the m compensated columns
+    as float64, hits[k] the index of dimension k among them or -1; the sum left to right with every product and sum rounded,
+    then arcsinh, then the logicle scale - ListMode's and TransformedPoints' one implementation."""
+    for k, i in enumerate(hits):
+        if i >= 0:
+            v = xs[0] * t.comp[0, i]
+            for j in range(1, t.m):
+                v = v + xs[j] * t.comp[j, i]
+            out[:, k] = v
+    if cofactors is not None:
+        with np.errstate(all="ignore"):
+            for k, cf in enumerate(cofactors.tolist()):
+                if cf > 0:
+                    out[:, k] = np.arcsinh(out[:, k] / cf)
+    if logicle is not None:
+        for k, row in enumerate(logicle):
+            if row[0] != 0:
+                out[:, k] = logicle_host(out[:, k], row)
+    return out
+
+
+class TransformedPoints(object):
+    """An [n, d] array of points with a ListTransform the device applies while it takes them in (the `_view_xl` entry points):
+    what ListMode(..., transform=...) is for `.fcs` events, for the arrays a parsed CSV, a `.npy` file or a caller hands over.
+    transform.comp_cols index the ARRAY's columns 0 .. d - 1 - every compensated column is a dimension -, cofactor and
+    logicle hold one entry / one row per column (or one for all).  The contract is ListTransform's: the left-to-right sum in
+    double, arcsinh(v / cofactor) or the logicle scale, a dimension takes one or the other.
+    An array points_view accepts - the nine element types, rows or columns form, C-contiguous float32 / float64 included - is
+    read where it lies; anything else is copied once, here, to C-contiguous float64 and that copy is read.
+    shape == (n, d), ndim == 2; np.asarray(points) applies the transform on the host (always float64), by the implementation
+    ListMode has: the device's compensation bit for bit, its asinh and logicle solve to a few units in the last place - where
+    the very values matter, read them back (Handle.points_download)."""
+
+    ndim = 2
+
+    def __init__(self, array, transform):
+        array = np.asarray(array)
+        if array.ndim != 2:
+            raise ValueError("TransformedPoints: the points must be a 2-d array")
+        self.array = array
+        self.shape = tuple(int(v) for v in array.shape)
+        self.transform = transform
+        self._cofactors, self._logicle = _transform_rows(transform, self.shape[1], "TransformedPoints")
+        # what the library reads: the array where it lies, or a C-contiguous float64 copy of it
+        self.points = array if points_view(array) is not None or self.shape[0] == 0 else _f64(array)
+
+    def __len__(self):
+        return self.shape[0]
+
+    def descriptor(self):
+        """The cc_points_view of these points (it points into this object: keep it alive while the descriptor is used)."""
+        view = points_view(self.points)
+        return view if view is not None else CcPointsView(None, self.shape[0], self.shape[1], DT_F64, max(self.shape[1], 1), 1)
+
+    transform_descriptor = ListMode.transform_descriptor
+    logicle_descriptor = ListMode.logicle_descriptor
+
+    def __array__(self, dtype=None, copy=None):
+        t = self.transform
+        out = np.array(self.array, dtype=np.float64, order="C")
+        if t is not None:
+            cols = t.comp_cols.tolist()
+            if any(c < 0 or c >= self.shape[1] for c in cols):
+                raise ValueError("TransformedPoints: a compensated column is outside 0..%d" % (self.shape[1] - 1))
+            xs = [np.asarray(self.array[:, c], dtype=np.float64) for c in cols]
+            hits = [cols.index(k) if k in cols else -1 for k in range(self.shape[1])]
+            out = _host_transform(out, xs, hits, t, self._cofactors, self._logicle)
+        return out if dtype is None else out.astype(dtype, copy=False)
 
 
 LOGICLE_STEPS = 4  # (CC_LOGICLE_STEPS of csrc/cc_ingest_list_xf.h)
@@ -473,6 +535,11 @@ SYMBOLS = {
     "cc_online_view": (C.c_int, [C.c_void_p, _vp, _i64p, _i8p]),
     "cc_assign_view": (C.c_int, [C.c_void_p, _vp, _i64p, _i8p, _dp]),
     "cc_view_points": (C.c_int, [C.c_void_p, _i64p]),
+    "cc_points_upload_view_xl": (C.c_int, [C.c_void_p, _vp, _xp, _gp, _dp, _dp]),
+    "cc_points_prefetch_view_xl": (C.c_int, [C.c_void_p, _vp, _xp, _gp, _dp, _dp]),
+    "cc_col_minmax_view_xl": (C.c_int, [C.c_void_p, _vp, _xp, _gp, _dp, _dp]),
+    "cc_online_view_xl": (C.c_int, [C.c_void_p, _vp, _xp, _gp, _i64p, _i8p]),
+    "cc_assign_view_xl": (C.c_int, [C.c_void_p, _vp, _xp, _gp, _i64p, _i8p, _dp]),
     "cc_points_upload_list": (C.c_int, [C.c_void_p, _lp, _dp, _dp]),
     "cc_points_prefetch_list": (C.c_int, [C.c_void_p, _lp, _dp, _dp]),
     "cc_col_minmax_list": (C.c_int, [C.c_void_p, _lp, _dp, _dp]),
@@ -782,22 +849,23 @@ def shard_rows(n, world, rank, unit=1):
 
 # The takers of points by kind of source (Handle._source): (operation, kind) -> C-ABI symbol.  A described source ("view",
 # "list", "list_xf": a ListMode with a transform, "list_xl": one whose transform has a logicle row that is on) has one upload that
-# takes scale / min_ or two nulls; rows have a plain and a scaled one.
-_DESCRIBED = ("view", "list", "list_xf", "list_xl")
+# takes scale / min_ or two nulls; rows have a plain and a scaled one.  "view_xl": a TransformedPoints.
+_DESCRIBED = ("view", "view_xl", "list", "list_xf", "list_xl")
+SOURCE_OBJECTS = (ListMode, TransformedPoints)  # what describes its own points: never copied, never handed to points_source
 _INGEST = {
     "upload": {"f64": "cc_points_upload", "f32": "cc_points_upload_f32",
-               "view": "cc_points_upload_view", "list": "cc_points_upload_list", "list_xf": "cc_points_upload_list_xf",
-               "list_xl": "cc_points_upload_list_xl"},
+               "view": "cc_points_upload_view", "view_xl": "cc_points_upload_view_xl", "list": "cc_points_upload_list",
+               "list_xf": "cc_points_upload_list_xf", "list_xl": "cc_points_upload_list_xl"},
     "upload_scaled": {"f64": "cc_points_upload_scaled", "f32": "cc_points_upload_scaled_f32",
-                      "view": "cc_points_upload_view", "list": "cc_points_upload_list", "list_xf": "cc_points_upload_list_xf",
-                      "list_xl": "cc_points_upload_list_xl"},
+                      "view": "cc_points_upload_view", "view_xl": "cc_points_upload_view_xl", "list": "cc_points_upload_list",
+                      "list_xf": "cc_points_upload_list_xf", "list_xl": "cc_points_upload_list_xl"},
     "prefetch": {"f64": "cc_points_prefetch", "f32": "cc_points_prefetch_f32",
-                 "view": "cc_points_prefetch_view", "list": "cc_points_prefetch_list", "list_xf": "cc_points_prefetch_list_xf",
-                 "list_xl": "cc_points_prefetch_list_xl"},
+                 "view": "cc_points_prefetch_view", "view_xl": "cc_points_prefetch_view_xl", "list": "cc_points_prefetch_list",
+                 "list_xf": "cc_points_prefetch_list_xf", "list_xl": "cc_points_prefetch_list_xl"},
     "col_minmax": {"f64": "cc_col_minmax", "f32": "cc_col_minmax_f32",
-                   "view": "cc_col_minmax_view", "list": "cc_col_minmax_list", "list_xf": "cc_col_minmax_list_xf",
-                   "list_xl": "cc_col_minmax_list_xl"},
-    "assign": {"f64": "cc_assign", "f32": "cc_assign_f32", "view": "cc_assign_view", "list": "cc_assign_list",
+                   "view": "cc_col_minmax_view", "view_xl": "cc_col_minmax_view_xl", "list": "cc_col_minmax_list",
+                   "list_xf": "cc_col_minmax_list_xf", "list_xl": "cc_col_minmax_list_xl"},
+    "assign": {"f64": "cc_assign", "f32": "cc_assign_f32", "view": "cc_assign_view", "view_xl": "cc_assign_view_xl", "list": "cc_assign_list",
                "list_xf": "cc_assign_list_xf", "list_xl": "cc_assign_list_xl"},
 }
 _SCALED_REFUSAL = "points must be [n, d], scale and min_ [d]"
@@ -853,7 +921,7 @@ class Handle(object):
 
     def _source(self, x, refusal="points must be a 2-d array"):
         """(kind, points, args, n, d) of what a taker of points is given: the kind of source - "list" (a ListMode; "list_xf"
-        with a transform, "list_xl" with a logicle row that is on), "view"
+        with a transform, "list_xl" with a logicle row that is on), "view_xl" (a TransformedPoints), "view"
         (an array points_view accepts), "f32" or "f64" (C-contiguous rows; everything else as a float64 copy: points_source) -,
         the object that owns the memory, and the C arguments that describe it: (descriptor,) or (pointer, n, d)."""
         if isinstance(x, ListMode):
@@ -863,6 +931,10 @@ class Handle(object):
             if xf is not None:
                 return ("list_xf", x, (C.byref(desc), C.byref(xf))) + x.shape
             return ("list", x, (C.byref(desc),)) + x.shape
+        if isinstance(x, TransformedPoints):
+            # (the array where it lies, or the object's own float64 copy; the library takes a null transform or null rows)
+            view, xf, lg = x.descriptor(), x.transform_descriptor(), x.logicle_descriptor()
+            return ("view_xl", x, (C.byref(view), None if xf is None else C.byref(xf), None if lg is None else C.byref(lg))) + x.shape
         x, view = points_source(x)
         if x.ndim != 2:
             raise ValueError(refusal)
@@ -898,11 +970,11 @@ class Handle(object):
 
     def points_prefetch(self, x, scale=None, min_=None):
         """Starts the background upload of the NEXT timepoint's points (cc_points_prefetch).  `x` must be the very
-        array (C-contiguous float64 or float32, or one points_view accepts) or ListMode that is later passed to points_upload /
+        array (C-contiguous float64 or float32, or one points_view accepts), ListMode or TransformedPoints that is later passed to points_upload /
         points_upload_scaled / online; the handle keeps a reference to it until then.  Contract: the array must not be
         written to between this call and that upload - the upload is recognised by pointer, shape, layout, element type and
         scaling, and the copy already on the device is used as it is."""
-        if isinstance(x, (np.ndarray, ListMode)) and x.ndim == 2 and x.shape[0] == 0:
+        if isinstance(x, (np.ndarray,) + SOURCE_OBJECTS) and x.ndim == 2 and x.shape[0] == 0:
             return
         refusal = ("points_prefetch needs an [n, d] array that is taken as it lies - C-contiguous float64 or float32, "
                    "or a layout and element type points_view accepts (it is not copied)")

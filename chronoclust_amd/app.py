@@ -205,8 +205,8 @@ def write_datapoints_details(dataset_attributes, clusters, hddstream, raw, clust
     if scaler:
         # the reference writes inverse_transform(transform(raw)), not raw: (X - min_) / scale_ on the device
         values = hddstream.resident_points(scaler.scale_, scaler.min_)
-    elif isinstance(raw, _lib.ListMode):
-        # (event records decoded - with a `.transform` sidecar also compensated and arcsinh-transformed or put on the logicle
+    elif isinstance(raw, _lib.SOURCE_OBJECTS):
+        # (event records decoded, or an array with its transform - with a `.transform` sidecar also compensated and arcsinh-transformed or put on the logicle
         # scale - on the device: read back, as under scaling; the host decode agrees with the device's asinh and logicle solve
         # only to the last place or two)
         values = hddstream.resident_points()

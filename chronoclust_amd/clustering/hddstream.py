@@ -128,7 +128,7 @@ class HDDStream(object):
         """device_scaling=(scale_, min_): `input_dataset` holds raw values and MinMaxScaler.transform
         (X * scale_ + min_) is applied on the device during the upload (scaling/scaler.py:39-41)."""
         # (an array the library reads where it lies stays as it is: the device widens it; so do list-mode event records)
-        X = input_dataset if isinstance(input_dataset, _lib.ListMode) else _lib.points_source(input_dataset)[0]
+        X = input_dataset if isinstance(input_dataset, _lib.SOURCE_OBJECTS) else _lib.points_source(input_dataset)[0]
         if X.ndim != 2:
             raise ValueError("input_dataset must be 2-d [N, d]")
         if reset_param:
@@ -154,7 +154,7 @@ class HDDStream(object):
         log.info("Starting online microcluster maintenance for timepoint {}".format(input_dataset_daystamp))
         progress = _progress_lines(log, X.shape[0])  # hddstream.py:218-220: tqdm's bar, written to the log
         # scaled values, and event records the device decoded, are fetched from the device on demand
-        self._X = X if device_scaling is None and not isinstance(X, _lib.ListMode) else None
+        self._X = X if device_scaling is None and not isinstance(X, _lib.SOURCE_OBJECTS) else None
         self._n_points = X.shape[0]
         try:
             if X.shape[0] > 0 and device_scaling is not None:
@@ -183,7 +183,7 @@ class HDDStream(object):
         current one.  Returns the array to pass to online_microcluster_maintenance (the same buffer, so that the upload
         is recognised); results never depend on whether a timepoint was prefetched.  The returned array must not be
         modified before it is passed on: the device copy made here is the one that gets clustered."""
-        X = input_dataset if isinstance(input_dataset, _lib.ListMode) else _lib.points_source(input_dataset)[0]
+        X = input_dataset if isinstance(input_dataset, _lib.SOURCE_OBJECTS) else _lib.points_source(input_dataset)[0]
         if X.ndim == 2 and X.shape[0] > 0:
             if device_scaling is None:
                 self._h.points_prefetch(X)
@@ -270,7 +270,7 @@ class HDDStream(object):
         (uid, path) with uid the creation number of the microcluster it would join (-1: it would create one) and path 0
         pcore / 1 outlier / 5 outlier that the add would promote / 2 new.  Every point is scored on its own against the
         microclusters as they stand; nothing of the model changes (Handle.assign)."""
-        X = input_dataset if isinstance(input_dataset, _lib.ListMode) else _lib.points_source(input_dataset)[0]
+        X = input_dataset if isinstance(input_dataset, _lib.SOURCE_OBJECTS) else _lib.points_source(input_dataset)[0]
         if X.ndim != 2:
             raise ValueError("input_dataset must be 2-d [N, d]")
         self._assign_params()

@@ -4,7 +4,7 @@
 // handle's state is written: not the table, the control block, the resident points or their labels, the window buffers, the
 // scan copies or the policy's carried state; of cc_stats only assign_points and assign_launches.  No collective is called:
 // on a handle of a group the rank's own table is read.  float64 rows are copied, checked and transposed chunk by chunk; every
-// other source (IngestSrc: cc_assign_f32, cc_assign_view, cc_assign_list, cc_assign_list_xf, cc_assign_list_xl) takes the same chunks, each staged through the set's
+// other source (IngestSrc: cc_assign_f32, cc_assign_view, cc_assign_view_xl, cc_assign_list, cc_assign_list_xf, cc_assign_list_xl) takes the same chunks, each staged through the set's
 // raw buffer and taken in by its ingest kernel (stage_slab, ingest_launch: cc_api_ingest.inc) - float32 rows a chunk at once, a
 // view or event records in sub-slabs of at most 16 MiB.  (included by cc_api.hip, the one translation unit, behind
 // cc_api_ingest.inc)
@@ -65,9 +65,9 @@ int assign_run(cc_handle* h, const IngestSrc& src, int64_t* out_uid, int8_t* out
         b.bad.ensure(4);
         HIPCHK(hipMemsetAsync(b.bad.p, 0, 16, st[q]));
     }
-    if (src.kind == IngestSrc::LIST) {
-        // the descriptors once, for both streams
-        list_desc_upload(h->stream, src.list, h->list_desc);
+    if (const ListSrc* ds = src.described()) {
+        // the descriptors (a view's transform) once, for both streams
+        list_desc_upload(h->stream, *ds, h->list_desc);
         sync_stream(h, h->stream);
     }
     std::vector<char> pack;
@@ -145,12 +145,18 @@ extern "C" int cc_assign_f32(cc_handle* h, const float* x, int64_t n, int32_t d,
     return assign_points(h, IngestSrc::rows(x, true, n, d), out_uid, out_path, out_dist);
 }
 
-extern "C" int cc_assign_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path, double* out_dist)
+extern "C" int cc_assign_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                                 int64_t* out_uid, int8_t* out_path, double* out_dist)
 {
     ViewSrc v;
-    const int rc = view_check(h, view, false, &v);
+    const int rc = view_check(h, view, xf, lg, false, &v);
     if (rc != CC_OK) return rc;
     return assign_points(h, IngestSrc::of(v), out_uid, out_path, out_dist);
+}
+
+extern "C" int cc_assign_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path, double* out_dist)
+{
+    return cc_assign_view_xl(h, view, nullptr, nullptr, out_uid, out_path, out_dist);
 }
 
 extern "C" int cc_assign_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transform* xf, const cc_list_logicle* lg,

@@ -72,14 +72,15 @@ size_t fill_pinned(const IngestSrc& s, int64_t off, int64_t ns, char* pin)
 
 // The source's ingest kernel on `st` for the ns points of a slab in device staging (`raw`: as stage_slab laid it out, or
 // `tight`, as fill_pinned did) that starts at point s0 of n_total: rows s0 .. of X [n_total, d], columns s0 .. of
-// Xt [xt_rows, n_total].  desc: the event records' descriptors on the device; scale / mn: device, or both null.
+// Xt [xt_rows, n_total].  desc: the event records' descriptors / a view's transform on the device (IngestSrc::described);
+// scale / mn: device, or both null.
 void ingest_launch(hipStream_t st, const IngestSrc& s, const void* raw, bool tight, const int* desc, int64_t ns, int64_t s0,
                    int64_t n_total, size_t xt_rows, double* X, double* Xt, const double* scale, const double* mn, int* bad)
 {
     switch (s.kind) {
     case IngestSrc::VIEW:
         return ingest_view_launch(st, raw, s.view.dtype, s.view.cols, s.view_pitch(ns, tight), ns, s0, n_total, s.d, xt_rows, X, Xt,
-                                  scale, mn, bad);
+                                  scale, mn, bad, s.view.tr, desc);
     case IngestSrc::LIST: return ingest_list_launch(st, raw, s.list, desc, ns, s0, n_total, xt_rows, X, Xt, scale, mn, bad);
     default: return ingest_f32_launch(st, static_cast<const float*>(raw), ns, s0, n_total, s.d, xt_rows, X, Xt, scale, mn, bad);
     }
@@ -133,7 +134,7 @@ int upload_source(cc_handle* h, const IngestSrc& src, const double* scale, const
             const size_t pb = src.point_bytes(false);
             const int64_t slab = std::min<int64_t>(slab_points(h, pb, CC_UPLOAD_STAGING), tiles_up(n));
             for (int q = 0; q < (n > slab ? 2 : 1); ++q) h->ingest_raw[q].ensure(slab_floats(pb, slab));
-            if (src.kind == IngestSrc::LIST) list_desc_upload(h->stream, src.list, h->list_desc);
+            if (const ListSrc* ds = src.described()) list_desc_upload(h->stream, *ds, h->list_desc);
             std::vector<char> pack;
             int k = 0;
             for (int64_t off = 0; off < n; off += slab, k ^= 1) {
@@ -172,7 +173,7 @@ void prefetch_worker(cc_handle::Prefetch& pf, int device, size_t xt_rows)
     const int d = s.d;
     const double* sc = pf.scaled ? pf.sm.p : nullptr;
     chk(hipMemsetAsync(pf.bad.p, 0, 16, pf.stream), "hipMemsetAsync");
-    if (s.kind == IngestSrc::LIST) chk(list_desc_copy(pf.stream, s.list, pf.desc.p), "hipMemcpyAsync");
+    if (const ListSrc* ds = s.described()) chk(list_desc_copy(pf.stream, *ds, pf.desc.p), "hipMemcpyAsync");
     if (pf.scaled) {
         chk(hipMemcpyAsync(pf.sm.p, pf.scale.data(), (size_t)d * 8, hipMemcpyHostToDevice, pf.stream), "hipMemcpyAsync");
         chk(hipMemcpyAsync(pf.sm.p + d, pf.mn.data(), (size_t)d * 8, hipMemcpyHostToDevice, pf.stream), "hipMemcpyAsync");
@@ -229,7 +230,7 @@ int prefetch_source(cc_handle* h, const IngestSrc& src, const double* scale, con
         pf.pin_bytes = CC_PREFETCH_STAGING;
     }
     pf.X.ensure((size_t)n * d); pf.Xt.ensure((size_t)n * xt_dims(d)); pf.sm.ensure((size_t)2 * d); pf.bad.ensure(4);
-    if (src.kind == IngestSrc::LIST) pf.desc.ensure(src.list.desc_words());
+    if (const ListSrc* ds = src.described()) pf.desc.ensure(ds->desc_words());
     if (src.staged()) {
         // a piece: the whole point tiles that fit a page-locked buffer, a view's rows without their pitch
         const size_t pb = src.point_bytes(true);
@@ -255,7 +256,7 @@ int col_minmax_slabs(cc_handle* h, const IngestSrc& src, double* out_min, double
     const size_t per_slab = (size_t)2 * chunks_of(slab) * d;
     for (int q = 0; q < (n > slab ? 2 : 1); ++q) h->ingest_raw[q].ensure(slab_floats(pb, slab));
     h->scr2.ensure(per_slab * (size_t)slabs);
-    if (src.kind == IngestSrc::LIST) list_desc_upload(h->stream, src.list, h->list_desc);
+    if (const ListSrc* ds = src.described()) list_desc_upload(h->stream, *ds, h->list_desc);
     std::vector<char> pack;
     int k = 0;
     int64_t si = 0;
@@ -266,7 +267,7 @@ int col_minmax_slabs(cc_handle* h, const IngestSrc& src, double* out_min, double
         if (src.kind == IngestSrc::LIST)
             minmax_list_launch(h->stream, src.list, h->ingest_raw[k].p, h->list_desc.p, ns, part, chunks_of(ns));
         else
-            minmax_view_launch(h->stream, src.view, h->ingest_raw[k].p, ns, part, chunks_of(ns));
+            minmax_view_launch(h->stream, src.view, h->ingest_raw[k].p, h->list_desc.p, ns, part, chunks_of(ns));
     }
     HIPCHK(hipGetLastError());
     std::vector<double> part(per_slab * (size_t)slabs);

@@ -2,9 +2,17 @@
 // element types) to the device without a copy there.  Here: the descriptor's check (view_check -> ViewSrc, cc_ingest_src.h),
 // how a slab of a view is staged (view_stage) and the launches of k_ingest and k_col_minmax_view (cc_ingest.h) for a staged
 // slab.  The upload, the prefetch and the column reduction themselves are those of every staged source (cc_api_ingest.inc);
-// cc_assign_view is in cc_api_assign.inc.  (included by cc_api.hip, the one translation unit, behind cc_api_points.inc)
+// cc_assign_view is in cc_api_assign.inc.  With a transform (the `_view_xl` entry points: cc_list_transform, cc_list_logicle,
+// checked by the list mode's own list_check_xf / list_check_lg over the view's d columns) the launches are those of
+// cc_ingest_xf.h: k_ingest_xf / k_col_minmax_view_xf for the columns form, the list kernels for the rows form, whose rows are
+// event records.  (included by cc_api.hip, the one translation unit, behind cc_api_points.inc)
 
 namespace {
+
+// (cc_api_list.inc, behind this file)
+int list_check_xf(cc_handle* h, const cc_list_transform* xf, ListSrc* out);
+int list_check_lg(cc_handle* h, const cc_list_logicle* lg, ListSrc* out);
+cc_list_xf list_xf_device(const ListSrc& v, const int* desc);
 
 int dtype_size(int dtype)
 {
@@ -71,6 +79,25 @@ int view_check(cc_handle* h, const cc_points_view* v, bool need_points, ViewSrc*
     return (int)CC_OK;
 }
 
+// view_check, then the transform's and the logicle rows' refusals as a list mode's: what every `_view_xl` entry point begins
+// with.  The compensated columns index the view's columns, so one outside 0 .. d - 1 is refused as one outside a record is.
+// xf and lg null, or a transform that asks for nothing: no transform - the `_view` sibling.
+int view_check(cc_handle* h, const cc_points_view* v, const cc_list_transform* xf, const cc_list_logicle* lg, bool need_points,
+               ViewSrc* out)
+{
+    int rc = view_check(h, v, need_points, out);
+    if (rc != CC_OK || (!xf && !lg)) return rc;
+    ListSrc& t = out->tr;
+    t.n = out->n; t.src_cols = out->d; t.dtype = out->dtype; t.sz = out->sz; t.flags = 0; t.d = out->d;
+    t.desc.resize((size_t)out->d);
+    for (int i = 0; i < out->d; ++i) {
+        t.desc[i].col = i;
+        t.desc[i].mask = 0xFFFFFFFFu;
+    }
+    rc = list_check_xf(h, xf, &t);
+    return rc != CC_OK ? rc : list_check_lg(h, lg, &t);
+}
+
 // Points off .. off + ns - 1 of the view into device staging `raw` on `st`, as view.pitch(ns) lays them out: whole pitched
 // rows in one copy (the last row only as far as its d elements), rows of a wasteful pitch packed on the host first (`pack`;
 // the copy has left it when this returns), or d strips.
@@ -93,11 +120,31 @@ void view_stage(hipStream_t st, const ViewSrc& v, int64_t off, int64_t ns, void*
 }
 
 // k_ingest on `st` for the ns points of a slab in device staging (`raw`, laid out by view_stage or by the prefetch worker at
-// a pitch of rp elements) that starts at point s0 of n_total; scale / mn: device, or both null
+// a pitch of rp elements) that starts at point s0 of n_total; scale / mn: device, or both null.  tr: the view's transform, with
+// one (tr.xf; desc: where list_desc_copy laid it on the device) k_ingest_xf for the columns form and k_ingest_list_xf over
+// records of rp elements for the rows form
 void ingest_view_launch(hipStream_t st, const void* raw, int dtype, bool cols, int64_t rp, int64_t ns, int64_t s0, int64_t n_total,
-                        int d, size_t xt_rows, double* X, double* Xt, const double* scale, const double* mn, int* bad)
+                        int d, size_t xt_rows, double* X, double* Xt, const double* scale, const double* mn, int* bad,
+                        const ListSrc& tr, const int* desc)
 {
     const dim3 grid((unsigned)((ns + CC_INGEST_TILE - 1) / CC_INGEST_TILE), (unsigned)((d + CC_INGEST_TILE - 1) / CC_INGEST_TILE));
+    if (tr.xf) {
+        const cc_list_xf xf = list_xf_device(tr, desc);
+        with_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            with_bools([&](auto L) {
+                if (cols)
+                    hipLaunchKernelGGL((k_ingest_xf<T, decltype(L)::value>), grid, dim3(256), 0, st, static_cast<const T*>(raw),
+                                       (long long)rp, (int)ns, (long long)s0, (long long)n_total, d, (int)xt_rows, xf, X, Xt, scale, mn,
+                                       bad);
+                else
+                    hipLaunchKernelGGL((k_ingest_list_xf<T, false, decltype(L)::value>), grid, dim3(256), 0, st,
+                                       static_cast<const unsigned char*>(raw), (int)rp, (int)ns, (long long)s0, (long long)n_total, d,
+                                       (int)xt_rows, reinterpret_cast<const cc_list_desc*>(desc), xf, X, Xt, scale, mn, bad);
+            }, tr.lg);
+        });
+        return;
+    }
     with_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         with_bools([&](auto C, auto S) {
@@ -109,10 +156,29 @@ void ingest_view_launch(hipStream_t st, const void* raw, int dtype, bool cols, i
 }
 
 // k_col_minmax_view on `st` for the ns points of a slab in device staging (`raw`, laid out by view_stage): its partials
-// part[2][chunks][d]
-void minmax_view_launch(hipStream_t st, const ViewSrc& v, const void* raw, int64_t ns, double* part, int chunks)
+// part[2][chunks][d]; with a transform (v.tr.xf; desc: where it lies on the device) over the transformed values:
+// k_col_minmax_view_xf for the columns form, k_col_minmax_list_xf over records of the staged pitch for the rows form
+void minmax_view_launch(hipStream_t st, const ViewSrc& v, const void* raw, const int* desc, int64_t ns, double* part, int chunks)
 {
     const int d = v.d;
+    if (v.tr.xf) {
+        const cc_list_xf xf = list_xf_device(v.tr, desc);
+        with_dtype(v.dtype, [&](auto t) {
+            using T = decltype(t);
+            with_bools([&](auto L) {
+                if (v.cols)
+                    hipLaunchKernelGGL((k_col_minmax_view_xf<T, decltype(L)::value>),
+                                       dim3(chunks, (d + CC_MINMAX_XF_DIMS - 1) / CC_MINMAX_XF_DIMS), dim3(256), 0, st,
+                                       static_cast<const T*>(raw), (long long)ns, d, (long long)v.pitch(ns), xf, part, chunks);
+                else
+                    hipLaunchKernelGGL((k_col_minmax_list_xf<T, false, decltype(L)::value>),
+                                       dim3(chunks, (d + CC_INGEST_TILE - 1) / CC_INGEST_TILE), dim3(256), 0, st,
+                                       static_cast<const unsigned char*>(raw), (long long)ns, (int)v.pitch(ns), d,
+                                       reinterpret_cast<const cc_list_desc*>(desc), xf, part, chunks);
+            }, v.tr.lg);
+        });
+        return;
+    }
     with_dtype(v.dtype, [&](auto t) {
         using T = decltype(t);
         const T* xd = static_cast<const T*>(raw);
@@ -129,40 +195,65 @@ void minmax_view_launch(hipStream_t st, const ViewSrc& v, const void* raw, int64
 
 extern "C" {
 
-int cc_points_upload_view(cc_handle* h, const cc_points_view* view, const double* scale, const double* min_)
+int cc_points_upload_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                             const double* scale, const double* min_)
 {
     if (!h || !view || ((scale == nullptr) != (min_ == nullptr))) return CC_ERR_BAD_ARG;
     ViewSrc v;
-    const int rc = view_check(h, view, false, &v);
+    const int rc = view_check(h, view, xf, lg, false, &v);
     if (rc != CC_OK) return rc;
     return guarded(h, [&]() { return upload_source(h, IngestSrc::of(v), scale, min_); });
 }
 
-int cc_points_prefetch_view(cc_handle* h, const cc_points_view* view, const double* scale, const double* min_)
+int cc_points_prefetch_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                               const double* scale, const double* min_)
 {
     if (!h || !view || ((scale == nullptr) != (min_ == nullptr))) return CC_ERR_BAD_ARG;
     ViewSrc v;
-    const int rc = view_check(h, view, true, &v);
+    const int rc = view_check(h, view, xf, lg, true, &v);
     if (rc != CC_OK) return rc;
     return guarded(h, [&]() { return prefetch_source(h, IngestSrc::of(v), scale, min_); });
 }
 
-int cc_col_minmax_view(cc_handle* h, const cc_points_view* view, double* out_min, double* out_max)
+int cc_col_minmax_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                          double* out_min, double* out_max)
 {
     if (!h || !view || !out_min || !out_max) return CC_ERR_BAD_ARG;
     ViewSrc v;
-    const int rc = view_check(h, view, true, &v);
+    const int rc = view_check(h, view, xf, lg, true, &v);
     if (rc != CC_OK) return rc;
     return guarded(h, [&]() { return col_minmax_slabs(h, IngestSrc::of(v), out_min, out_max); });
 }
 
-int cc_online_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path)
+int cc_online_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                      int64_t* out_uid, int8_t* out_path)
 {
-    int rc = cc_points_upload_view(h, view, nullptr, nullptr);
+    int rc = cc_points_upload_view_xl(h, view, xf, lg, nullptr, nullptr);
     if (rc != CC_OK) return rc;
     rc = cc_online_run(h);
     if (rc != CC_OK) return rc;
     return cc_labels_download(h, out_uid, out_path);
+}
+
+// the `_view` entry points: their `_xl` siblings without a transform
+int cc_points_upload_view(cc_handle* h, const cc_points_view* view, const double* scale, const double* min_)
+{
+    return cc_points_upload_view_xl(h, view, nullptr, nullptr, scale, min_);
+}
+
+int cc_points_prefetch_view(cc_handle* h, const cc_points_view* view, const double* scale, const double* min_)
+{
+    return cc_points_prefetch_view_xl(h, view, nullptr, nullptr, scale, min_);
+}
+
+int cc_col_minmax_view(cc_handle* h, const cc_points_view* view, double* out_min, double* out_max)
+{
+    return cc_col_minmax_view_xl(h, view, nullptr, nullptr, out_min, out_max);
+}
+
+int cc_online_view(cc_handle* h, const cc_points_view* view, int64_t* out_uid, int8_t* out_path)
+{
+    return cc_online_view_xl(h, view, nullptr, nullptr, out_uid, out_path);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // cc_ingest_src.h — what the host knows of points that reach the device through staging: IngestSrc, one description for
-// float32 rows (`_f32`), a checked cc_points_view (`_view`) and a checked cc_list_mode (`_list`, `_list_xf`, `_list_xl`), with float64 rows - a
+// float32 rows (`_f32`), a checked cc_points_view (`_view`; with a checked transform: `_view_xl`) and a checked cc_list_mode (`_list`, `_list_xf`, `_list_xl`), with float64 rows - a
 // whole-array copy, not staged - as its fourth kind.  The upload, the prefetch and cc_assign (cc_api_ingest.inc,
 // cc_api_assign.inc) are written once against it; cc_handle::Prefetch keeps one to tell which upload may adopt it.
 // Host data only: the staging copies and the kernel launches per kind are in cc_api_ingest.inc.
@@ -7,22 +7,6 @@
 #pragma once
 
 namespace {
-
-// a checked cc_points_view
-struct ViewSrc {
-    const char* data = nullptr;
-    int64_t n = 0;
-    int d = 0, dtype = 0, sz = 0;
-    int64_t rs = 0, cs = 0;
-    bool cols = false;
-    // rows form whose pitch would waste the bus (beyond 8 d elements): the slab's rows are packed on the host first
-    bool packed() const { return !cols && rs > 8 * (int64_t)d; }
-    // elements from a staged point to the next (rows form) / from a staged strip to the next (columns form) for ns points
-    int64_t pitch(int64_t ns) const { return cols ? ((ns + 63) & ~(int64_t)63) : (packed() ? d : rs); }
-    // bytes of staging a point takes
-    size_t point_bytes() const { return (size_t)(cols || packed() ? d : rs) * sz; }
-    const char* at(int64_t r, int64_t c) const { return data + (r * rs + c * cs) * sz; }
-};
 
 // a checked cc_list_mode: the descriptors with their defaults filled in
 struct ListSrc {
@@ -45,6 +29,26 @@ struct ListSrc {
     bool swapped() const { return (flags & CC_LM_SWAPPED) != 0; }
     size_t record_bytes() const { return (size_t)src_cols * (size_t)sz; }
     const char* at(int64_t r) const { return data + (size_t)r * record_bytes(); }
+};
+
+// a checked cc_points_view
+struct ViewSrc {
+    const char* data = nullptr;
+    int64_t n = 0;
+    int d = 0, dtype = 0, sz = 0;
+    int64_t rs = 0, cs = 0;
+    bool cols = false;
+    // the transform of the `_view_xl` entry points (cc_list_transform / cc_list_logicle, checked by list_check_xf / list_check_lg
+    // as a list mode's are): carried as a ListSrc over the view's d columns - src_cols = d, the identity descriptors, no mask -, so
+    // that it is laid out on the device, compared and read by the kernels as a list mode's is.  tr.xf: there is one.
+    ListSrc tr;
+    // rows form whose pitch would waste the bus (beyond 8 d elements): the slab's rows are packed on the host first
+    bool packed() const { return !cols && rs > 8 * (int64_t)d; }
+    // elements from a staged point to the next (rows form) / from a staged strip to the next (columns form) for ns points
+    int64_t pitch(int64_t ns) const { return cols ? ((ns + 63) & ~(int64_t)63) : (packed() ? d : rs); }
+    // bytes of staging a point takes
+    size_t point_bytes() const { return (size_t)(cols || packed() ? d : rs) * sz; }
+    const char* at(int64_t r, int64_t c) const { return data + (r * rs + c * cs) * sz; }
 };
 
 struct IngestSrc {
@@ -94,19 +98,26 @@ struct IngestSrc {
     bool same(const IngestSrc& o) const
     {
         if (kind != o.kind || x != o.x || n != o.n || d != o.d) return false;
-        if (kind == VIEW) return view.dtype == o.view.dtype && view.rs == o.view.rs && view.cs == o.view.cs;
+        if (kind == VIEW)
+            return view.dtype == o.view.dtype && view.rs == o.view.rs && view.cs == o.view.cs && same_transform(view.tr, o.view.tr);
         if (kind != LIST) return true;
         if (list.dtype != o.list.dtype || list.src_cols != o.list.src_cols || list.flags != o.list.flags) return false;
         for (int i = 0; i < d; ++i)
             if (list.desc[i].col != o.list.desc[i].col || list.desc[i].mask != o.list.desc[i].mask) return false;
-        // the transform by content: m, the columns, the bits of every matrix entry, cofactor and logicle row
-        if (list.xf != o.list.xf || list.m != o.list.m || list.has_cof != o.list.has_cof || list.xf_i != o.list.xf_i ||
-            list.xf_f.size() != o.list.xf_f.size() || list.lg != o.list.lg || list.lg_twma.size() != o.list.lg_twma.size())
-            return false;
-        if (!list.lg_twma.empty() && memcmp(list.lg_twma.data(), o.list.lg_twma.data(), list.lg_twma.size() * sizeof(double)) != 0)
-            return false;
-        return list.xf_f.empty() || memcmp(list.xf_f.data(), o.list.xf_f.data(), list.xf_f.size() * sizeof(double)) == 0;
+        return same_transform(list, o.list);
     }
+    // the transform by content: m, the columns, the bits of every matrix entry, cofactor and logicle row
+    static bool same_transform(const ListSrc& a, const ListSrc& b)
+    {
+        if (a.xf != b.xf || a.m != b.m || a.has_cof != b.has_cof || a.xf_i != b.xf_i || a.xf_f.size() != b.xf_f.size() || a.lg != b.lg ||
+            a.lg_twma.size() != b.lg_twma.size())
+            return false;
+        if (!a.lg_twma.empty() && memcmp(a.lg_twma.data(), b.lg_twma.data(), a.lg_twma.size() * sizeof(double)) != 0) return false;
+        return a.xf_f.empty() || memcmp(a.xf_f.data(), b.xf_f.data(), a.xf_f.size() * sizeof(double)) == 0;
+    }
+    // what lies on the device beside the points for the kernels to read, once per call: a list mode's descriptors with its
+    // transform behind them, a view's transform (laid out the same way), else nothing
+    const ListSrc* described() const { return kind == LIST ? &list : (kind == VIEW && view.tr.xf ? &view.tr : nullptr); }
 };
 
 }  // namespace

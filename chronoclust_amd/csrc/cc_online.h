@@ -235,4 +235,5 @@ __device__ __forceinline__ double cc_sel_scale(unsigned mask, double scaled, dou
 #include "cc_ingest_list.h"  // ... and of list-mode event records: either byte order, a list of channels
 #include "cc_logicle.h"  // ... (the coefficients of the logicle scale, derived on the host)
 #include "cc_ingest_list_xf.h"  // ... and of event records that are compensated and arcsinh-transformed on the way
+#include "cc_ingest_xf.h"  // ... and of a point view that takes the same transform: the columns form, the view types' bit patterns
 #include "cc_negq.h"  // ... and the exact quantile of their negative compensated values, pooled: the logicle width W

@@ -183,13 +183,19 @@ def parse_spillover(text, names):
 def _compensation(text, names):
     """(channel indices, inverse spillover matrix) for read_fcs(compensate=True)."""
     key, idx, spill = parse_spillover(text, names)
+    return idx, invert_spillover(spill, "FCS TEXT: the matrix of %s" % key)
+
+
+def invert_spillover(spill, what):
+    """The inverse of a spillover matrix (numpy.linalg.inv) as the transform takes it - the one place it is inverted, for the
+    file's own keyword (read_fcs) and for a sidecar's "spillover" (array_transform).  ValueError `what` is singular."""
     try:
         inv = np.linalg.inv(spill)
     except np.linalg.LinAlgError:
-        raise ValueError("FCS TEXT: the matrix of %s is singular" % key) from None
+        raise ValueError("%s is singular" % what) from None
     if not np.isfinite(inv).all():
-        raise ValueError("FCS TEXT: the matrix of %s is singular" % key)
-    return idx, np.ascontiguousarray(inv)
+        raise ValueError("%s is singular" % what)
+    return np.ascontiguousarray(inv)
 
 
 def _cofactors(cofactor, picked):
@@ -425,7 +431,11 @@ def sidecar_transform(path):
     {"compensate": bool, "cofactor": number | {channel name: number}, "logicle": {"T": number, "W": .., "M": .., "A": ..} |
     {channel name: {...}}}, every key optional (and every key of a logicle object: read_fcs has the defaults); the returned
     dict carries "logicle" only where the file does.  A logicle object's W may be "estimate", with an optional "q" beside it:
-    the width is then taken from the events of the whole run (estimate_sidecars, which app.run calls)."""
+    the width is then taken from the events of the whole run (estimate_sidecars, which app.run calls).
+    Beside a `.csv` or `.npy` timepoint one more key is taken, "spillover": {"channels": [names], "matrix": [[...]]} - square,
+    finite, one row and one column per channel -, the matrix "compensate" then inverts (array_transform): such a file has no
+    $SPILLOVER of its own.  The returned dict carries it only where the file does.  Beside an `.fcs` file the key is refused:
+    the file's own spillover keyword is the contract there."""
     import json
     import os
     name = str(path) + ".transform"
@@ -436,7 +446,10 @@ def sidecar_transform(path):
             spec = json.load(f)
         except ValueError as e:
             raise ValueError("%s: not JSON (%s)" % (name, e)) from None
-    if not isinstance(spec, dict) or set(spec) - {"compensate", "cofactor", "logicle"} or \
+    if isinstance(spec, dict) and "spillover" in spec and str(path).lower().endswith(".fcs"):
+        raise ValueError('%s: "spillover" is for .csv and .npy timepoints; an .fcs file is compensated by its own spillover '
+                         'keyword (%s)' % (name, ", ".join(SPILLOVER_KEYWORDS)))
+    if not isinstance(spec, dict) or set(spec) - {"compensate", "cofactor", "logicle", "spillover"} or \
             ("logicle" in spec and not _is_logicle_spec(spec["logicle"])):
         raise ValueError('%s: expected {"compensate": bool, "cofactor": number or {name: number}, "logicle": {T, W, M, A: number} '
                          'or {name: {T, W, M, A: number}}}' % name)
@@ -449,7 +462,82 @@ def sidecar_transform(path):
     out = dict(compensate=compensate, cofactor=cofactor)
     if "logicle" in spec:
         out["logicle"] = spec["logicle"]
+    if "spillover" in spec:
+        out["spillover"] = _sidecar_spillover(name, spec["spillover"])
     return out
+
+
+def _sidecar_spillover(name, spill):
+    """(channel names, matrix [n, n]) of a sidecar's "spillover" object; ValueError naming the key for a malformed one."""
+    ok = isinstance(spill, dict) and set(spill) == {"channels", "matrix"} and isinstance(spill["channels"], list) and \
+        len(spill["channels"]) > 0 and all(isinstance(c, str) for c in spill["channels"]) and isinstance(spill["matrix"], list)
+    if not ok:
+        raise ValueError('%s: "spillover" must be {"channels": [names], "matrix": [[numbers]]}' % name)
+    n = len(spill["channels"])
+    if n > MAX_COMP:
+        raise ValueError('%s: "spillover" names %d channels, at most %d are taken' % (name, n, MAX_COMP))
+    if len(set(spill["channels"])) != n:
+        raise ValueError('%s: "spillover" names a channel twice' % name)
+    rows = spill["matrix"]
+    if len(rows) != n or any(not isinstance(r, list) or len(r) != n for r in rows):
+        raise ValueError('%s: the matrix of "spillover" is not square: %d channels need %d rows of %d numbers' % (name, n, n, n))
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for r in rows for v in r):
+        raise ValueError('%s: the matrix of "spillover" holds a value that is no number' % name)
+    matrix = np.array(rows, np.float64).reshape(n, n)
+    if not np.isfinite(matrix).all():
+        raise ValueError('%s: the matrix of "spillover" holds a value that is not finite' % name)
+    return list(spill["channels"]), matrix
+
+
+def array_transform(path, names, compensate=False, cofactor=None, logicle=None, spillover=None):
+    """The `_lib.ListTransform` a `.csv` or `.npy` timepoint's sidecar asks for (sidecar_transform's keywords), over the
+    array's columns `names` - the CSV header, `<file>.columns` for a `.npy` -, or None where it asks for nothing: what
+    read_fcs builds for an `.fcs` file from its TEXT segment.  compensate needs "spillover" - there is no $SPILLOVER to read -,
+    whose channels are matched against `names` and whose matrix is inverted by the function read_fcs uses; cofactor and
+    logicle by name resolve against `names`; a logicle row must carry T - there is no $PnR to default to - and a W of
+    "estimate" is refused: the estimate selects over list-mode events only.  ValueError naming the key or the channel."""
+    name = str(path) + ".transform"
+    names = list(names)
+    comp_idx = inv = None
+    if compensate:
+        if spillover is None:
+            raise ValueError('%s: "compensate" needs "spillover": {"channels": [names], "matrix": [[...]]} - a .csv or .npy '
+                             'timepoint has no spillover keyword of its own' % name)
+        channels, matrix = spillover
+        for ch in channels:
+            if ch not in names:
+                raise ValueError('%s: "spillover" names channel %r, which is no column (columns: %s)' % (name, ch, ", ".join(names)))
+        comp_idx = [names.index(ch) for ch in channels]
+        inv = invert_spillover(matrix, '%s: the matrix of "spillover"' % name)
+    try:
+        cof = _cofactors(cofactor, names)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, e)) from None
+    rows = None
+    if logicle is not None:
+        if not _is_logicle_spec(logicle):
+            raise ValueError("%s: logicle must be {T, W, M, A: number} or {channel name: such an object}" % name)
+        by_name = not _is_logicle_row(logicle)
+        for k, ch in enumerate(names):
+            row = logicle.get(ch) if by_name else (None if cof is not None and cof[k] > 0 else logicle)
+            if row is None:
+                continue
+            if _is_unresolved(row):
+                raise ValueError('%s: the logicle scale of channel %s has "W": "estimate": the width is estimated from list-mode '
+                                 '(.fcs) events only, not for .csv or .npy timepoints - give W as a number' % (name, ch))
+            if "T" not in row:
+                raise ValueError('%s: the logicle scale of channel %s needs "T": a .csv or .npy timepoint has no $PnR to take '
+                                 "it from" % (name, ch))
+        try:
+            rows = _logicles(logicle, names, list(range(len(names))), cof, {})
+        except ValueError as e:
+            raise ValueError("%s: %s" % (name, e)) from None
+    if comp_idx is None and cof is None and (rows is None or not (rows[:, 0] != 0).any()):
+        return None
+    try:
+        return ListTransform(comp_cols=comp_idx, comp=inv, cofactor=cof, logicle=rows)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, e)) from None
 
 
 def logicle_w(count, lo, hi, frac, T, M):

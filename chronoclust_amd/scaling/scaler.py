@@ -8,7 +8,7 @@ tests/test_host_logic.py checks bit equality against scikit-learn."""
 import numpy as np
 import pandas as pd
 
-from .._lib import ListMode, points_source
+from .._lib import SOURCE_OBJECTS, TransformedPoints, points_source
 
 
 def read_timepoint(filename, logicle=None):
@@ -20,7 +20,10 @@ def read_timepoint(filename, logicle=None):
     $PnS) selects and orders the channels, without it all channels are taken in file order; `<file>.transform` (JSON:
     {"compensate": bool, "cofactor": number | {name: number}, "logicle": {T, W, M, A} | {name: {T, W, M, A}}},
     fcs.sidecar_transform) asks for the file's own spillover compensation and arcsinh(x / cofactor) or the logicle scale,
-    applied on the device as the events land (read_fcs).  logicle: {path: logicle rows by channel name} - the rows that take
+    applied on the device as the events land (read_fcs).  Beside a `.csv` or `.npy` timepoint `<file>.transform` takes the same
+    keys and "spillover": {"channels": [names], "matrix": [[...]]} in the place of the file's own keyword (fcs.array_transform;
+    names: the CSV header, `<file>.columns` for a `.npy`); the timepoint then comes back as a `_lib.TransformedPoints`, which
+    the device compensates and transforms as it takes the array in.  logicle: {path: logicle rows by channel name} - the rows that take
     the place of the sidecar's for that file: what fcs.estimate_sidecars resolved where a sidecar holds "W": "estimate"."""
     if str(filename).lower().endswith(".fcs"):
         from ..fcs import read_fcs, sidecar_columns, sidecar_transform
@@ -28,10 +31,20 @@ def read_timepoint(filename, logicle=None):
         if logicle and filename in logicle:
             kw = dict(kw, logicle=logicle[filename])
         return read_fcs(filename, columns=sidecar_columns(filename), **kw)[0]
+    from ..fcs import array_transform, sidecar_columns, sidecar_transform
+    kw = sidecar_transform(filename)
     if str(filename).endswith(".npy"):
         X = np.load(filename)
-        return np.ascontiguousarray(X, dtype=np.float32 if X.dtype == np.float32 else np.float64)
-    return pd.read_csv(filename, header=0, sep=',').to_numpy()
+        X = np.ascontiguousarray(X, dtype=np.float32 if X.dtype == np.float32 else np.float64)
+        names = sidecar_columns(filename) if kw else None
+        if kw and (names is None or len(names) != X.shape[1]):
+            raise ValueError("%s.transform needs %s.columns with one name per column (%d)" % (filename, filename, X.shape[1]))
+    else:
+        frame = pd.read_csv(filename, header=0, sep=',')
+        X, names = frame.to_numpy(), [str(c) for c in frame.columns]
+    # (`<file>.transform` beside a CSV or .npy: the transform rides with the array and the device applies it - _view_xl)
+    transform = array_transform(filename, names, **kw) if kw else None
+    return X if transform is None else TransformedPoints(X, transform)
 
 
 class Scaler(object):
@@ -50,7 +63,7 @@ class Scaler(object):
                 # (kept as parsed where the library reads it where it lies - pandas hands a CSV out column-major -, else as
                 # a C-contiguous float64 copy)
                 X = read_timepoint(filename, logicle)
-                if not isinstance(X, ListMode):  # (event records of an FCS file: the handle reads them where they lie)
+                if not isinstance(X, SOURCE_OBJECTS):  # (event records, an array with its transform: read where they lie)
                     X = points_source(X)[0]
                 self.parsed[filename] = X
                 if X.shape[0] == 0:

@@ -423,6 +423,37 @@ int cc_assign_list_xl(cc_handle* h, const cc_list_mode* lm, const cc_list_transf
                       int8_t* out_path, double* out_dist);
 int cc_logicle_coefficients(const double twma[4], double out[8]);
 
+/* Point views, compensated and arcsinh- or logicle-transformed on the device: the transform contract of the `_list_xf` and
+ * `_list_xl` entry points, unchanged, for the arrays a parsed CSV, a .npy file or a caller hands over.  Per value: (double) of
+ * the element, exact for every view type; then the compensation - the same left-to-right sum in double, nothing fused -;
+ * then asinh(v / cofactor) - one double division, the device maths library's asinh - OR the logicle scale - the same solve with
+ * its compile-time step count -; then scale / min_, the finiteness flag, the magnitude maximum and both resident copies, which
+ * hold the same doubles (each value is computed once).  A view's row of d elements is read as an event record whose selected
+ * dimensions are its columns 0 .. d - 1: what the device then holds is bit for bit what the `_list_xl` entry points hold after
+ * the same values laid out as float64 event records.
+ * xf and lg are the structures of the list-mode entry points as they are: comp_cols index the VIEW's columns 0 .. d - 1 - every
+ * compensated column is therefore a selected dimension, and there are no masks -; cofactor and twma hold one entry / one row
+ * per column of the view.
+ * Each entry point is its `_view` sibling with a transform; xf == NULL && lg == NULL, or a transform that asks for nothing
+ * (m == 0, cofactor == NULL, every T == 0), IS the sibling.  Refused with CC_ERR_BAD_ARG and a message that names the reason,
+ * before anything is read or launched, beside the sibling's refusals: everything the `_list_xf` / `_list_xl` entry points
+ * refuse about xf and lg, with the view's d in the place of src_cols - so a compensated column outside 0 .. d - 1 - and of the
+ * selected dimensions.  A NaN in a compensated column, or a compensated sum that overflows, refuses the upload with
+ * CC_ERR_NONFINITE.  A prefetch is adopted only by the upload of the same view with the same transform: m, the columns and
+ * the bits of every matrix entry, cofactor and logicle row.  cc_col_minmax_view_xl reduces the transformed, unscaled values -
+ * the very doubles the plain upload holds.  cc_view_points counts these points too; a group of ranks behaves as with the
+ * `_view` siblings. */
+int cc_points_upload_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                             const double* scale, const double* min_);
+int cc_points_prefetch_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                               const double* scale, const double* min_);
+int cc_col_minmax_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                          double* out_min, double* out_max);
+int cc_online_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                      int64_t* out_uid, int8_t* out_path);
+int cc_assign_view_xl(cc_handle* h, const cc_points_view* view, const cc_list_transform* xf, const cc_list_logicle* lg,
+                      int64_t* out_uid, int8_t* out_path, double* out_dist);
+
 /* An exact order statistic per selected column over the NEGATIVE compensated values of list-mode events, pooled over any number
  * of sources and selected on the device: what the rule of Parks, Roederer and Moore 2006 takes the logicle width from
  * (W = (M - log10(T / |r|)) / 2, r the 5th percentile of a channel's negative values - the caller's arithmetic).
