@@ -66,6 +66,7 @@ struct Table {
 };
 #define CC_HEAVY_CAP 64   // heavy rows at a time (= workgroups of a k_claims_heavy launch)
 #define CC_HEAVY_NEW 32   // candidates a window may nominate
+#define CC_STAMP_SLOTS 64 // Ctl::scan_t0 / scan_t1: a power of two above the windows one batch can hold
 
 // Candidate slots >= CC_CAR_BASE refer to carried rows (index = slot - CC_CAR_BASE), below to version rows.
 #define CC_CAR_BASE (1 << 24)
@@ -253,6 +254,15 @@ struct Ctl {
     int n_heavy, n_heavy_new;
     int heavy_list[CC_HEAVY_CAP];
     int heavy_new[CC_HEAVY_NEW];
+    // Time stamps of the in-place snapshot scans (time_kernels = 1), from the device's constant-rate clock: window `seq` owns
+    // slot seq & (CC_STAMP_SLOTS - 1).  scan_t0: stored by the first kernel of the window's scan chain that finds the slot
+    // at 0 (cc_stamp_begin); scan_t1: stored by k_decide round 0, the first kernel behind every form of the chain;
+    // k_commit_a of window seq zeroes both stamps of slot seq + 1.  A window that does not run leaves scan_t0 at 0.  The
+    // host reads them with the control block after every batch (fewer than CC_STAMP_SLOTS windows) and zeroes all of them
+    // whenever it writes the block.  stamp_on = 0: nobody stores any.
+    unsigned long long scan_t0[CC_STAMP_SLOTS], scan_t1[CC_STAMP_SLOTS];
+    int stamp_on;
+    int pad4;
 #ifdef CC_LONG_TIMERS
     unsigned long long dbg_long[8];  // build variant: shader cycles per phase of k_chain_long (workgroup 0 of each launch)
 #endif
@@ -283,6 +293,33 @@ struct Ctl {
                            // scan that ran does not cover the outlier kind for this point
 #define CC_FLAG_SPARSE 64  // the point is on the round's list of points whose dirty scans run point by point (the sparse
                            // dirty scans: compacted tiles of such points, both kinds covered) although its tile's did not
+
+// The begin stamp of an in-place snapshot scan (Ctl::scan_t0): called behind the early returns of every kernel that can be
+// the first of such a chain (mode 0 only: a lookahead scan belongs to another window than Ctl::window_seq names).  One lane
+// of the launch looks; the chain's kernels run in stream order, so the first one stores and the later ones find the slot
+// taken.  The block is an argument of every kernel already - const in most, and none of them reads these fields.  With
+// time_kernels = 0 that is one scalar load and a branch in one lane of one workgroup, and the clock is not read.
+// (Reading the clock as the kernel's first statement instead was built and measured: it rearranged the prologue of every
+// wave of the scan kernels and cost the untimed step 0.2 ms - profiles/scan_stamps_ab.txt.)
+__device__ __forceinline__ void cc_stamp_begin(const Ctl* ctl)
+{
+    if (blockIdx.x != 0 || blockIdx.y != 0 || threadIdx.x != 0) return;
+    if (ctl->stamp_on == 0) return;
+    Ctl* const c = const_cast<Ctl*>(ctl);
+    const int s = (int)(c->window_seq & (unsigned long long)(CC_STAMP_SLOTS - 1));
+    if (c->scan_t0[s] == 0ull) c->scan_t0[s] = (unsigned long long)wall_clock64();
+}
+// The end stamp: k_decide round 0, its one lane that takes the window's counters over, behind that - the chain in front of the
+// launch has drained.  Only behind a begin stamp: a window that does not run has neither.  The begin stamp is taken three
+// dependent loads into its kernel; this one sits behind as many and the counters' stores, so that the interval errs towards
+// long (by a round trip to memory or two) and not towards shorter than the chain it brackets.
+__device__ __forceinline__ void cc_stamp_end(Ctl* ctl)
+{
+    if (ctl->stamp_on == 0) return;
+    const int s = (int)(*(const volatile unsigned long long*)&ctl->window_seq & (unsigned long long)(CC_STAMP_SLOTS - 1));
+    if (*(const volatile unsigned long long*)&ctl->scan_t0[s] == 0ull) return;
+    ctl->scan_t1[s] = (unsigned long long)wall_clock64();
+}
 
 // (cc_shard_share / cc_shard_range: cc_host.h - plain C++, shared with the host-only sanitizer build)
 __host__ __device__ inline bool cand_less(double ad, int ak, double bd, int bk)

@@ -311,6 +311,7 @@ struct cc_handle : Knobs, BatchScanState, PrunedScanBuffers, WindowBuffers, Offl
     DevBuf<double> seq_img;     // [4][d][table capacity] k_seq_g: dimension-major copy of the rows it scans (centroid, operand, CF1, CF2)
     bool seq_sticky = false;    // the last call ended on the sequential kernel (k_seq): the next one starts there
     int n_cus = 256;            // compute units of the device (hipDeviceProp_t::multiProcessorCount)
+    int wall_khz = 0;           // rate of the device's constant clock (hipDeviceAttributeWallClockRate; 0: unknown, no stamps)
 
     // points + labels of the current call
     DevBuf<double> X, Xt;
@@ -469,10 +470,18 @@ void refresh_ctl_params(cc_handle* h)
 
 // (Every push opens a fresh window chain - start of a call, back from the sequential kernel, a restart -: whatever scans
 // left per window parity belongs to windows that will be scanned again, and the host's copy of it may be a half-summed one.)
+// (The scan stamps go with it: the host has counted those of every window that ran before it writes the block, so no stamp
+// outlives the batch - or the call - it was taken in.)
+void clear_window_chain(Ctl& c)
+{
+    memset(c.pstat, 0, sizeof(c.pstat));
+    c.n_missed_all[0] = c.n_missed_all[1] = 0;
+    memset(c.scan_t0, 0, sizeof(c.scan_t0));
+    memset(c.scan_t1, 0, sizeof(c.scan_t1));
+}
 void push_ctl(cc_handle* h)
 {
-    memset(h->hc.pstat, 0, sizeof(h->hc.pstat));
-    h->hc.n_missed_all[0] = h->hc.n_missed_all[1] = 0;
+    clear_window_chain(h->hc);
     HIPCHK(hipMemcpyAsync(h->ctl.p, &h->hc, sizeof(Ctl), hipMemcpyHostToDevice, h->stream));
 }
 void pull_ctl(cc_handle* h)
@@ -495,8 +504,7 @@ void pull_ctl_pinned(cc_handle* h)
 void push_ctl_pinned(cc_handle* h)
 {
     if (!h->hc_pin) { push_ctl(h); return; }
-    memset(h->hc.pstat, 0, sizeof(h->hc.pstat));
-    h->hc.n_missed_all[0] = h->hc.n_missed_all[1] = 0;
+    clear_window_chain(h->hc);
     memcpy(h->hc_pin + 1, &h->hc, sizeof(Ctl));
     HIPCHK(hipMemcpyAsync(h->ctl.p, h->hc_pin + 1, sizeof(Ctl), hipMemcpyHostToDevice, h->stream));
 }

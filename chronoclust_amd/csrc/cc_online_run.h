@@ -216,6 +216,13 @@ struct OnlineRun {
     size_t ev_used = 2, ev_sync = ev_base;
     std::vector<std::pair<size_t, double>> timed;  // (event index, 1.0 for a pruned chain)
     std::vector<size_t> timed_comm;                // event index of every timed merge + all-gather
+    // In-place scans (one stream, not split, no lookahead) are timed without events: two stamps of the device's constant
+    // clock per window, taken inside kernels that run anyway (Ctl::scan_t0 / scan_t1) and read with the control block after
+    // the batch.  An event record costs the stream ~6 us of idle device at each of the two places, a stamp nothing.
+    bool stamps = false;                                      // this call's control block has stamp_on set
+    std::vector<std::pair<unsigned long long, int>> stamped;  // the batch's windows timed that way: (sequence number, 1 for a pruned chain)
+    int64_t stamped_n = 0, stamped_n_p = 0;                   // launches so timed in this call / of those, pruned chains
+    double stamped_ms = 0.0, stamped_ms_p = 0.0;              // their intervals, of the windows that ran
     double pair_rows_eff = 0.0, pair_rows_prev = 0.0;  // (window points x table rows) this rank's scans covered
     double pair_rows_pruned = 0.0;                     // ... of those, by pruned chains
     long long sharded_windows = 0;
@@ -345,6 +352,10 @@ struct OnlineRun {
         HIPCHK(hipMemsetAsync(h->tab.heavy.p, 0, h->tab.cap * sizeof(int), h->stream));  // (the marks behind Ctl::n_heavy)
         c.x_absmax = h->x_absmax;
         set_lookahead(dec.lookahead != 0);
+        timing = h->tun.time_kernels != 0;
+        // (a batch must fit the ring of stamp slots, and the clock's rate must be known: else the events time every scan)
+        stamps = timing && h->wall_khz > 0 && batch_max < (size_t)CC_STAMP_SLOTS;
+        c.stamp_on = stamps ? 1 : 0;
         push_ctl(h);
 
         // no carry set yet: the commit record of an earlier call describes rows that may have moved since
@@ -360,7 +371,6 @@ struct OnlineRun {
         ev0 = get_event(h, 0); ev1 = get_event(h, 1);
         HIPCHK(hipEventRecord(ev0, h->stream));
         ev_used = 2;
-        timing = h->tun.time_kernels != 0;
         shard_on = dec.shard != 0;
 
         ver = versions_view(h);
@@ -511,6 +521,14 @@ struct OnlineRun {
         // that is how the second all-gather is exercised over RCCL on one GPU)
         h->group_guess_now = shard_on && (sworld > 1 || h->group_guess_always);
         scan_end = nullptr;
+        if (stamps && mode == 0 && !shard_on && !la_on && stamped.size() + 1 < (size_t)CC_STAMP_SLOTS) {
+            // in place, one stream: the chain's first kernel and k_decide stamp the device clock (cc_stamp_begin / cc_stamp_end)
+            launch_scan<false>(h, st, gw, rws, nullptr, h->part.p, S, round, mode, srank, sworld);
+            stamped.push_back({seq_host, h->prune_now ? 1 : 0});
+            ++stamped_n;
+            if (h->prune_now) ++stamped_n_p;
+            return;
+        }
         if (timing) {
             hipEvent_t a = get_event(h, ev_used), b = get_event(h, ev_used + 1);
             HIPCHK(hipEventRecord(a, st));
@@ -723,6 +741,18 @@ struct OnlineRun {
         HIPCHK(hipGetLastError());
         pull_ctl_pinned(h);
         if (la_on) sync_stream(h, sB);
+        // the stamped scans of the windows that ran (a prefix of the batch: the device's sequence number has passed them); a
+        // window the device idled left its begin stamp at 0
+        for (const auto& s : stamped) {
+            if (s.first >= h->hc.window_seq) break;
+            const size_t slot = (size_t)(s.first & (unsigned long long)(CC_STAMP_SLOTS - 1));
+            const unsigned long long t0 = h->hc.scan_t0[slot], t1 = h->hc.scan_t1[slot];
+            if (t0 == 0ull || t1 <= t0) continue;
+            const double ms = (double)(t1 - t0) / (double)h->wall_khz;
+            stamped_ms += ms;
+            if (s.second) stamped_ms_p += ms;
+        }
+        stamped.clear();
         seq_host = h->hc.window_seq;
         done = h->hc.cursor;
         const double dt = now_ms() - batch_t0;
@@ -845,10 +875,11 @@ struct OnlineRun {
                 tot += e;
                 if (t.second != 0.0) { tot_p += e; ++n_p; }
             }
-            h->stats.scan_launches += (int64_t)timed.size();
-            h->stats.scan_ms += tot;
-            h->stats.scan_launches_pruned += n_p;
-            h->stats.scan_ms_pruned += tot_p;
+            // (the stamped scans were summed batch by batch, after_batch; launches are counted as enqueued either way)
+            h->stats.scan_launches += (int64_t)timed.size() + stamped_n;
+            h->stats.scan_ms += tot + stamped_ms;
+            h->stats.scan_launches_pruned += n_p + stamped_n_p;
+            h->stats.scan_ms_pruned += tot_p + stamped_ms_p;
             double ctot = 0.0;
             for (size_t i : timed_comm) {
                 float e = 0.f;

@@ -72,6 +72,7 @@ __global__ __launch_bounds__(64 * NW, (ScanShape<DP, DIRTY>::WGS)) void k_scan(c
         }
     }
     if (B == 0) return;
+    if (!DIRTY && mode == 0) cc_stamp_begin(ctl);
     if (DIRTY && ctl->fc[round - 1] >= B) return;  // already at a fixed point
     const bool carried = DIRTY && mode == 1;
     const int car_n = carried ? ((ctl->mode != 0) ? ctl->car_n : 0) : 0;
@@ -659,6 +660,7 @@ __global__ __launch_bounds__(64 * NW, ScanUShape<DP>::WGS) void k_scan_u(const C
     }
     part += (size_t)q * part_stride;
     if (B == 0) return;
+    if (mode == 0) cc_stamp_begin(ctl);
     // plist (round 6): not the window's tiles but the points a guessed-threshold scan missed (k_missed's / k_missed_g's list of
     // the window's parity).  Such a point has no microcluster within the guess: a seeded threshold of its own is as wide as
     // its nearest microcluster is far, the pruned chain completes most rows for it - one by one, each a chain of dependent
@@ -944,6 +946,7 @@ __global__ __launch_bounds__(256) void k_pad_rows(const Ctl* __restrict__ ctl, c
     constexpr int HP = DP / 2;
     const ScanWin win = cc_scan_window(ctl, round, mode);
     if (win.B == 0) return;
+    if (mode == 0) cc_stamp_begin(ctl);
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t row = t / HP;
     if (row >= (size_t)win.rows) return;
@@ -1014,6 +1017,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_seed(const Ctl* __restrict__ ctl
     const ScanWin win = cc_scan_window(ctl, round, mode);
     const int B = win.B;
     if (B == 0) return;
+    if (mode == 0) cc_stamp_begin(ctl);
     const int j0 = (int)blockIdx.x * 128;
     // (plist: not the window's points but the ones a guessed threshold missed, k_missed's list of the window's parity)
     if (plist) plist += (size_t)win.q * CC_MISSED_CAP;
@@ -1360,6 +1364,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_scan_a(const Ctl* __restrict__ c
     const ScanWin win = cc_scan_window(ctl, round, mode);
     const int B = win.B;
     if (B == 0) return;
+    if (mode == 0) cc_stamp_begin(ctl);  // (first where a guessed-threshold scan is split into phases A and B)
     const int j0 = (int)blockIdx.x * 128;
     if (j0 >= B) return;
     thr += (size_t)win.q * thr_stride;
@@ -1506,6 +1511,7 @@ __global__ __launch_bounds__(64 * NW, (DP <= 20 ? CC_SCANP_WGS20 : (DP <= 40 ? 3
     const ScanWin win = cc_scan_window(ctl, round, mode);
     const int B = win.B;
     if (B == 0) return;
+    if (mode == 0 && guess_F > 0.0) cc_stamp_begin(ctl);  // (guessed thresholds: nothing runs in front of the scan)
     const int j0 = (int)blockIdx.x * 64;
     // plist: the points a guessed threshold missed (k_missed's list of the window's parity) instead of the window's tiles
     if (plist) plist += (size_t)win.q * CC_MISSED_CAP;
@@ -1903,6 +1909,7 @@ __global__ __launch_bounds__(64 * NW, CC_SCANP2_WGS) void k_scan_p2(
     const ScanWin win = cc_scan_window(ctl, round, mode);
     const int B = win.B;
     if (B == 0) return;
+    if (mode == 0 && guess_F > 0.0) cc_stamp_begin(ctl);  // (guessed thresholds: nothing runs in front of the scan)
     const int j0 = (int)blockIdx.x * 128;
     if (j0 >= B) return;
     part += (size_t)win.q * part_stride;

@@ -119,6 +119,7 @@ __global__ __launch_bounds__(256) void k_prefix16(const Ctl* __restrict__ ctl, c
     constexpr int NP = Prefix16<DP>::NP;
     const ScanWin win = cc_scan_window(ctl, round, mode);
     if (win.B == 0) return;
+    if (mode == 0) cc_stamp_begin(ctl);
     a16 += (size_t)win.q * a16_stride;
     hdr += win.q;
     const double cmd = 2.0 * __builtin_fmax(ctl->x_absmax, __longlong_as_double((long long)ctl->cen_absmax));
@@ -218,6 +219,7 @@ __global__ __launch_bounds__(64 * NW, CC_SCANP3_WGS) void k_scan_p3(
     const ScanWin win = cc_scan_window(ctl, round, mode);
     const int B = win.B;
     if (B == 0) return;
+    if (mode == 0 && guess_F > 0.0) cc_stamp_begin(ctl);  // (guessed thresholds: nothing but k_prefix16 in front of the scan)
     const int j0 = (int)blockIdx.x * 128;
     if (j0 >= B) return;
     part += (size_t)win.q * part_stride;
@@ -643,6 +645,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_seed16(const Ctl* __restrict__ c
     const ScanWin win = cc_scan_window(ctl, round, mode);
     const int B = win.B;
     if (B == 0) return;
+    if (mode == 0) cc_stamp_begin(ctl);
     const int j0 = (int)blockIdx.x * 128;
     if (j0 >= B) return;
     spart += (size_t)win.q * spart_stride;

@@ -660,6 +660,7 @@ __global__ __launch_bounds__(256) void k_decide(Ctl* __restrict__ ctl, const dou
         // (atomic: the groups of this launch that refuse a point whose first place is a bound add to the same counter)
         if (ctl->n_missed_all[q] != 0) atomicAdd((unsigned long long*)&ctl->stat_missed, (unsigned long long)ctl->n_missed_all[q]);
         ctl->n_missed_all[q] = 0;
+        cc_stamp_end(ctl);  // (Ctl::scan_t1: the window's snapshot-scan chain has drained)
     }
     if (round > 0 && ctl->fc[round - 1] >= B) return;
     // a quiet round: k_dseed established that every point's decision repeats its claim (Ctl::rdiff).  Nothing to write:
@@ -2206,6 +2207,11 @@ __global__ __launch_bounds__(1024) void k_commit_a(Ctl* __restrict__ ctl, Table 
         ctl->stat_pair_rows += (double)B * (double)M0;
         // next window
         ctl->window_seq = seq + 1ull;
+        if (ctl->stamp_on != 0) {
+            const int s1 = (int)((seq + 1ull) & (unsigned long long)(CC_STAMP_SLOTS - 1));
+            ctl->scan_t0[s1] = 0ull;
+            ctl->scan_t1[s1] = 0ull;
+        }
         if ((ctl->la_on != 0 && !la_ok && next_b > 0) || n == 0) {
             // (n == 0: the first point could not be decided without the dirty scans the host had stopped launching)
             // no usable lookahead scan and, in a lookahead batch, no in-place scan either: wait for the host
